@@ -12,7 +12,8 @@ HBM.
 
     python bench.py [--gpus N [--rehearse]] [--steps K] [--warmup W]
                     [--workload config2|cornell10k|field100k_1080p|field100k|field1m]
-                    [--no-cpu-baseline] [--no-north-star] [--no-check]
+                    [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-north-star] [--no-config3] [--no-check]]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Parallel modes (the row split of SURVEY §8e, byte-identical frames for every N):
@@ -32,12 +33,26 @@ Parallel modes (the row split of SURVEY §8e, byte-identical frames for every N)
     rt580_dist.DistFrame over torch.distributed). --gpus must equal WORLD_SIZE.
 
 Rank 0 prints ONE JSON line on stdout: metric, value = whole-job Mrays/s,
-ms_per_step, roofline of the AO ray kernel, cpu_baseline (N = 1), the frame
-check of the last timed frame (config 2: the reference's sha256), the
-north_star sub-record (the 100k-triangle 1920x1080 depth-4 AO-64 frame that
-BASELINE's target names) and the config3 sub-record (BASELINE config 3, the
-10k-triangle Cornell box at 1920x1080 depth 4 AO 64), both measured the same
-way in the same run.
+ms_per_step, and the roofline of the AO ray kernel from the committed counter
+profile and the timed frames' own HIP events. A plain run does no more: it sets
+up, warms up, times the steps, writes the last timed frame if --dump-outputs is
+given, and prints the line.
+
+--full adds everything that takes runs of its own, after the timed region:
+cpu_baseline (N = 1), the frame check of the last timed frame (config 2: the
+reference's sha256; pixel segments against the oracle), the AO kernel's
+isolated launch timing, the blocking Render() latency, the north_star
+sub-record (the 100k-triangle 1920x1080 depth-4 AO-64 frame that BASELINE's
+target names) and the config3 sub-record (BASELINE config 3, the 10k-triangle
+Cornell box at 1920x1080 depth 4 AO 64), both measured the same way in the same
+run. --no-cpu-baseline, --no-north-star, --no-config3, --no-check and
+--no-render-call drop single parts of a --full run.
+
+--dump-outputs DIR writes what the last timed step left with its caller, the
+frame in host memory, as DIR/frame.npy (float32, height x width x 3; a frame
+above 32 MB as float32 is written as a fixed, seeded sample of its values). The
+scene is a file and the renderer's random stream is seeded, so the frame is the
+same from run to run.
 """
 import argparse
 import contextlib
@@ -163,9 +178,11 @@ class Ctx:
         return "1 GPU"
 
 
-def run_workload(ctx, name, steps, warmup, cpu_baseline_on, check):
+def run_workload(ctx, name, steps, warmup, cpu_baseline_on, check, dump_dir=None):
     """Render `name` warmup + steps times in ctx's parallel mode; returns the
-    bench record (rank 0) or None."""
+    bench record (rank 0) or None. Without --full the record holds what the
+    timed steps themselves measured; dump_dir: write the last timed frame there."""
+    full = ctx.args.full
     torch, lib, rt580, helpers = ctx.torch, ctx.lib, ctx.rt580, ctx.helpers
     scene, synth, W, H, depth, ao, label = WORKLOADS[name]
     root = helpers.synthetic_root(scene[:-5]) if synth else helpers.ASSETS_ROOT
@@ -309,6 +326,10 @@ def run_workload(ctx, name, steps, warmup, cpu_baseline_on, check):
         elif last is not None:
             rt580.check(lib.rt_gpu_synchronize(), "rt_gpu_synchronize")
             frame_np = last.copy().reshape(H, W, 3)
+    if dump_dir and ctx.rank == 0:
+        if frame_np is None:
+            raise SystemExit("bench.py: --dump-outputs: this step leaves no frame in host memory")
+        dump_outputs(dump_dir, frame_np.reshape(H, W, 3))
 
     if ctx.dist_on:
         t = torch.tensor([dt], dtype=torch.float64, device=ctx.device)
@@ -373,7 +394,7 @@ def run_workload(ctx, name, steps, warmup, cpu_baseline_on, check):
     # small-scene frame is one launch over all of its (this context's) AO rays
     k_units = k_rays.value if k_rays.value else int(local["rays_ao"]) * max(frames.value, 1)
     iso = None
-    if not ctx.dist_on and not ctx.multi and K == 1:
+    if full and not ctx.dist_on and not ctx.multi and K == 1:
         # after the timed region (and after the last frame was copied out): the
         # same frames with AO phases in frame order, so no other frame's AO
         # kernels run beside the timed launch -- its isolated duration
@@ -382,16 +403,16 @@ def run_workload(ctx, name, steps, warmup, cpu_baseline_on, check):
     # per-row AO-call counts of the frame from one untimed GPU count pass: the
     # RNG bases of the oracle's frame-check rows and of the CPU baseline's range
     row_counts = None
-    if frame_np is not None and not ctx.multi and not ctx.dist_on and \
+    if full and frame_np is not None and not ctx.multi and not ctx.dist_on and \
             ((check and ctx.args.check_pixels != 0) or cpu_baseline_on):
         row_counts = helpers.rt580_dist().GpuRows(rt580, params, torch, ctx.device).count(0, 1)[:H].cpu().numpy()
-    if frame_np is not None:
+    if full and frame_np is not None:
         out["frame_check"] = frame_check(ctx, name, frame_np, single, W, H, check)
         if check and row_counts is not None:
             n_px = ctx.args.check_pixels if ctx.args.check_pixels > 0 else CHECK_PIXELS[name]
             if n_px:
                 out["frame_check"].update(oracle_rows_check(ctx, name, root, frame_np, row_counts, n_px))
-    if not ctx.dist_on and not ctx.multi and K == 1 and not ctx.args.no_render_call:
+    if full and not ctx.dist_on and not ctx.multi and K == 1 and not ctx.args.no_render_call:
         out["render_call_ms"] = render_latency(lib, rt580, params, torch)
     for _, buf in ring:
         rt580.check(lib.rt_gpu_host_unregister(buf.ctypes.data), "rt_gpu_host_unregister")
@@ -560,6 +581,23 @@ def roofline(workload, k_ms, k_launches, k_rays, iso=None):
         if prof.get("avg_ms"):
             res["isolated_over_rocprof"] = round(iso["launch_ms"] / prof["avg_ms"], 4)
     return res
+
+
+DUMP_MAX_BYTES = 32 << 20  # of one dumped array
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: the last timed frame as dirname/frame.npy in float32.
+    A frame above DUMP_MAX_BYTES is written as a sample of its flattened
+    values at sorted indices drawn with a fixed seed (the same indices for the
+    same frame shape, so two builds' dumps compare value for value)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n_max = DUMP_MAX_BYTES // 4
+    if frame.size > n_max:
+        idx = np.sort(np.random.default_rng(580).integers(0, frame.size, n_max))
+        frame = frame.reshape(-1)[idx]
+    np.save(os.path.join(dirname, "frame.npy"), frame.astype(np.float32))
 
 
 RING = 3  # host frames of the one-process step (one per frame slot in flight)
@@ -736,6 +774,12 @@ def main():
     ap.add_argument("--steps", type=int, default=None,
                     help="default 20 (config2), 10 (synthetic 1080p), 3 (synthetic 4K / 8K)")
     ap.add_argument("--warmup", type=int, default=None, help="default 3")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own, after the timed steps: CPU baseline, frame checks against "
+                         "the reference's hash and the oracle, isolated AO-kernel timing, Render() latency, the "
+                         "north_star and config3 sub-records")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's frame (host memory) to DIR/frame.npy as float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-north-star", action="store_true", help="skip the north_star sub-record (config2)")
     ap.add_argument("--no-config3", action="store_true", help="skip the config3 sub-record (config2)")
@@ -771,6 +815,11 @@ def main():
         raise SystemExit("bench.py: need --row-sample K >= 1 and 0 <= --row-rank < K")
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and (args.row_sample > 1 or (args.step == "device" and args.gpus == 1 and not args.dist)):
+        raise SystemExit("bench.py: --dump-outputs needs a step that leaves the whole frame in host memory "
+                         "(not --row-sample, not --step device)")
     synth = WORKLOADS[args.workload][1]
     # 3 warmup frames: the first verifies the node capacity and records the
     # trace phase's host reads, the second the AO phase's; from the third on a
@@ -781,14 +830,15 @@ def main():
     warmup = args.warmup if args.warmup is not None else 3
 
     ctx = Ctx(args)
-    out = run_workload(ctx, args.workload, steps, warmup, not args.no_cpu_baseline, not args.no_check)
-    if args.workload == "config2" and not args.no_north_star:
-        ns = run_workload(ctx, "field100k_1080p", 10, 3, not args.no_cpu_baseline, not args.no_check)
+    cpu_on, check = args.full and not args.no_cpu_baseline, args.full and not args.no_check
+    out = run_workload(ctx, args.workload, steps, warmup, cpu_on, check, dump_dir=args.dump_outputs)
+    if args.full and args.workload == "config2" and not args.no_north_star:
+        ns = run_workload(ctx, "field100k_1080p", 10, 3, cpu_on, check)
         if out is not None:
             out["north_star"] = ns
-    if args.workload == "config2" and not args.no_config3:
+    if args.full and args.workload == "config2" and not args.no_config3:
         # BASELINE config 3, the other 1 x MI355X configuration, measured the same way
-        c3 = run_workload(ctx, "cornell10k", 10, 3, not args.no_cpu_baseline, not args.no_check)
+        c3 = run_workload(ctx, "cornell10k", 10, 3, cpu_on, check)
         if out is not None:
             out["config3"] = c3
     if out is not None:

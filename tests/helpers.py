@@ -17,7 +17,6 @@ ASSETS_ROOT = GOLDEN  # contains Assets/ (reference scene fixtures + synthetic s
 PKG = os.path.join(REPO, "580-raytracer_amd")
 ORACLE_DIR = os.path.join(REPO, "oracle")
 ORACLE_LIB = os.path.join(ORACLE_DIR, "_build", "librt_oracle.so")
-REFERENCE = "/root/reference/580 Raytracer"
 SCENES_ROOT = os.path.join(REPO, "tests", "_scenes")  # generated synthetic scenes (not committed)
 
 

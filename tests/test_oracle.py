@@ -1,7 +1,7 @@
 """The CPU restatement (oracle/) pinned against the reference's own outputs:
 golden PPMs produced by the reference binary (tests/golden/make_golden.py),
 the reference's committed output.ppm, and the BASELINE hashes."""
-import filecmp
+import json
 import os
 import subprocess
 
@@ -59,11 +59,14 @@ def test_oracle_faithful_mode_matches_golden(name):
     assert c_f == c_h
 
 
-@pytest.mark.skipif(not os.path.isdir(helpers.REFERENCE), reason="reference not mounted")
 def test_scene_fixtures_are_the_reference_assets():
-    ref = os.path.join(helpers.REFERENCE, "Assets")
-    for f in os.listdir(ref):
-        assert filecmp.cmp(os.path.join(ref, f), os.path.join(helpers.GOLDEN, "Assets", f), shallow=False), f
+    """Every file of the reference's Assets/ (its names and sha256 recorded in
+    tests/golden/reference_assets.json) is among the fixtures, byte for byte."""
+    want = json.load(open(os.path.join(helpers.GOLDEN, "reference_assets.json")))["sha256"]
+    assert len(want) == 9
+    for f, digest in want.items():
+        with open(os.path.join(helpers.GOLDEN, "Assets", f), "rb") as fh:
+            assert helpers.sha256(fh.read()) == digest, f
 
 
 @pytest.mark.parametrize("p0,n", [(0, 24 * 18), (24 * 5 + 7, 100)])

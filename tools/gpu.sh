@@ -57,6 +57,7 @@ suite)
   ;;
 bench)
   TAG=$1; shift
+  set -- --full "$@"  # the whole line: sub-records, frame checks, Render() latency, CPU baseline
   timeout -k 10 1000 python -u bench.py "$@" > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -8 gpurun_out/bench_$TAG.err; exit 1; }
   summary gpurun_out/bench_$TAG.json
   ;;
@@ -65,6 +66,7 @@ ab)
   SETS=()
   while [ $# -gt 0 ] && [ "$1" != "--" ]; do SETS+=("$1"); shift; done
   [ "${1:-}" = "--" ] && shift
+  set -- --full "$@"
   mkdir -p gpurun_out/ab
   i=0
   for E in "${SETS[@]}"; do
@@ -101,7 +103,7 @@ profile)
   mkdir -p $OUT
   # the step's frames only: no Render() latency frames (their AO runs in two launches,
   # which would mix half launches into the per-dispatch averages)
-  BENCH="python3 bench.py --no-cpu-baseline --no-north-star --no-config3 --no-check --no-render-call $*"
+  BENCH="python3 bench.py --full --no-cpu-baseline --no-north-star --no-config3 --no-check --no-render-call $*"
   case "$*" in *--steps*) ;; *) BENCH="$BENCH --steps 3 --warmup 1";; esac
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- $BENCH > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 1; }
   i=0
@@ -128,7 +130,7 @@ trace)
   TAG=$1; shift
   OUT=gpurun_out/trace_$TAG
   mkdir -p $OUT
-  BENCH="python3 bench.py --no-cpu-baseline --no-north-star --no-config3 --no-check $*"
+  BENCH="python3 bench.py --full --no-cpu-baseline --no-north-star --no-config3 --no-check $*"
   case "$*" in *--steps*) ;; *) BENCH="$BENCH --steps 6 --warmup 3";; esac
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- $BENCH > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 1; }
   python3 tools/trace_gaps.py $OUT/trace_kernel_trace.csv 4 > $OUT/gaps.txt && head -25 $OUT/gaps.txt
