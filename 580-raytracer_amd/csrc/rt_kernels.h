@@ -117,7 +117,8 @@ struct DevWork {
     void* sort_tmp;
     size_t sort_tmp_bytes;
     uint32_t far_cap;
-    // split AO pass (ao_trace_kernel): (o.xyz, call), (d.xyz, flag) per item of a chunk
+    // split AO pass (ao_trace_kernel): (v.xyz, call in the chunk | flag << 30) per item of a
+    // chunk, v the sample's unnormalized direction; ao_record rebuilds (o, d) from it and ao_hp
     float4* ao_rays;       // [ao_cap] 16-byte AO ray records of a chunk (ao_record) or null
     float4* ao_hp;         // [ao_cap + 2]: the hit point of each call of the chunk (after ao_rays)
     uint32_t ao_cap;

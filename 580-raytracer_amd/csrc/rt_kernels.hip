@@ -3659,7 +3659,7 @@ hipError_t launch_ao(const DevScene& S, const DevFrame& F, const DevWork& W, hip
                     return e;
             }
 #endif
-            // the samples' rays (32-byte records), then the budgeted near any-hit in
+            // the samples' rays (16-byte records + each call's hit point), then the budgeted near any-hit in
             // speculative form (ao_trace_kernel) and the late pass for the rays
             // out of budget (ao_late_kernel), timed together (kt_*)
             constexpr int V = 512 | 1024 | 2048 | 4096 | 16384;

@@ -1336,6 +1336,24 @@ static int ordered_d2h(HostRange* hr, void* host, const void* src, size_t bytes,
     return RT_SUCCESS;
 }
 
+// The PPM body of `world` interleaved u8 row tiles into the registered range hr
+// at `host`, on stream s after the previous write into the range: de-interleaved
+// straight into the range through its device mapping, or into `stage` and copied.
+static int body_to_host(const uint8_t* tiles, int world, int n_max, int W, int H, HostRange* hr, uint8_t* host,
+                        hipStream_t s, DevBuf& stage) {
+    HIP_TRY(hipStreamWaitEvent(s, hr->copied, 0));
+    if (uint8_t* dst = (uint8_t*)mapped(hr, host)) {
+        HIP_TRY(launch_deinterleave_u8(tiles, world, n_max, W, H, dst, s));
+    } else {
+        const size_t body = (size_t)W * H * 3;
+        if (ensure(stage, body)) return RT_FAILURE;
+        HIP_TRY(launch_deinterleave_u8(tiles, world, n_max, W, H, (uint8_t*)stage.p, s));
+        HIP_TRY(hipMemcpyAsync(host, stage.p, body, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipEventRecord(hr->copied, s));
+    return RT_SUCCESS;
+}
+
 static int render_device_frame(const rt_render_params* p, int16_t** fb_device, void* host, bool u8) {
     if (check_params(p)) return RT_FAILURE;
     HIP_TRY(hipSetDevice(g.device));
@@ -1352,7 +1370,7 @@ static int render_device_frame(const rt_render_params* p, int16_t** fb_device, v
     // The RNG offsets need every row before a selected one: render the prefix
     // [0, row_end) and copy the selected rows out when the selection is sparse.
     const int n_rows = prefix ? n_sel : p->row_end;
-    // (RT580_SMALL_SLOTS: the slots of whole small-scene frames, A/B; config 2
+    // (whole small-scene frames rotate over as many slots as the others: config 2
     // 1.478 ms with two, 1.460 with three)
     if (begin_slot(false, frame_uses_bvh(p) ? g.nslots : g.small_slots)) return RT_FAILURE;
     for (int attempt = 0; attempt < 4; attempt++) {
@@ -1649,12 +1667,10 @@ int rt_gpu_host_unregister(void* host_ptr) {
     return fail("rt_gpu_host_unregister: %p was not registered", host_ptr);
 }
 
-int rt_gpu_count_rows(const rt_render_params* p, uint32_t* row_calls_device) {
-    RT_WORK("rt_gpu_count_rows");
-    if (check_params(p)) return RT_FAILURE;
-    if (!row_calls_device) return fail("row_calls_device is NULL");
-    HIP_TRY(hipSetDevice(g.device));
-    const int n_rows = n_selected_rows(p);
+// Phase 1 of a split frame on the next frame slot: p's n_rows selected rows
+// traced, their AO calls counted into the slot's row_calls (traced again with
+// more node capacity when that ran out).
+static int count_pass(const rt_render_params* p, int n_rows) {
     if (begin_slot(false, g.nslots)) return RT_FAILURE;
     for (int attempt = 0; attempt < 4; attempt++) {
         if (begin_frame()) return RT_FAILURE;
@@ -1666,6 +1682,16 @@ int rt_gpu_count_rows(const rt_render_params* p, uint32_t* row_calls_device) {
         if (attempt == 3) return fail("node capacity could not be sized");
         if (g.profiling) g.prof_frames--;
     }
+    return RT_SUCCESS;
+}
+
+int rt_gpu_count_rows(const rt_render_params* p, uint32_t* row_calls_device) {
+    RT_WORK("rt_gpu_count_rows");
+    if (check_params(p)) return RT_FAILURE;
+    if (!row_calls_device) return fail("row_calls_device is NULL");
+    HIP_TRY(hipSetDevice(g.device));
+    const int n_rows = n_selected_rows(p);
+    if (count_pass(p, n_rows)) return RT_FAILURE;
     if (end_slot()) return RT_FAILURE;  // the caller's stream waits for the count pass
     // The counts go into the caller's buffer, which the caller may have just
     // allocated or cleared on its own stream (after the mark begin_slot waited
@@ -1680,15 +1706,21 @@ int rt_gpu_count_rows(const rt_render_params* p, uint32_t* row_calls_device) {
     return RT_SUCCESS;
 }
 
+// Phase 2 (`who`) follows rt_gpu_count_rows with the same params, on its slot,
+// which waits for the row bases: they were produced on the caller's stream.
+static int split_follows_count(const rt_render_params* p, const char* who) {
+    if (!g.split_ready || std::memcmp(&g.split_params, p, sizeof *p) != 0)
+        return fail("%s must follow rt_gpu_count_rows with the same params", who);
+    HIP_TRY(hipSetDevice(g.device));
+    g.split_ready = false;
+    return slot_wait_user();
+}
+
 int rt_gpu_shade_rows(const rt_render_params* p, const uint64_t* row_base_device, int16_t* fb_device) {
     RT_WORK("rt_gpu_shade_rows");
     if (check_params(p)) return RT_FAILURE;
     if (!row_base_device || !fb_device) return fail("row_base_device / fb_device is NULL");
-    if (!g.split_ready || std::memcmp(&g.split_params, p, sizeof *p) != 0)
-        return fail("rt_gpu_shade_rows must follow rt_gpu_count_rows with the same params");
-    HIP_TRY(hipSetDevice(g.device));
-    g.split_ready = false;
-    if (slot_wait_user()) return RT_FAILURE;  // the row bases were produced on the caller's stream
+    if (split_follows_count(p, "rt_gpu_shade_rows")) return RT_FAILURE;
     if (shade_rows(p, p->row_begin, p->row_step, n_selected_rows(p), row_base_device, fb_device)) return RT_FAILURE;
     return end_slot();
 }
@@ -1698,11 +1730,7 @@ int rt_gpu_shade_rows_ppm(const rt_render_params* p, const uint64_t* row_base_de
     RT_WORK("rt_gpu_shade_rows_ppm");
     if (check_params(p)) return RT_FAILURE;
     if (!row_base_device || !tile_u8_device) return fail("row_base_device / tile_u8_device is NULL");
-    if (!g.split_ready || std::memcmp(&g.split_params, p, sizeof *p) != 0)
-        return fail("rt_gpu_shade_rows_ppm must follow rt_gpu_count_rows with the same params");
-    HIP_TRY(hipSetDevice(g.device));
-    g.split_ready = false;
-    if (slot_wait_user()) return RT_FAILURE;  // the row bases were produced on the caller's stream
+    if (split_follows_count(p, "rt_gpu_shade_rows_ppm")) return RT_FAILURE;
     const size_t n = (size_t)n_selected_rows(p) * p->width * 3;
     if (ensure(SL.fb, n * 2)) return RT_FAILURE;  // the slot's own int16 rows
     if (shade_rows(p, p->row_begin, p->row_step, n_selected_rows(p), row_base_device, (int16_t*)SL.fb.p))
@@ -1739,17 +1767,7 @@ int rt_gpu_deinterleave_ppm(const uint8_t* tiles, int world, int n_max, int widt
     const size_t body = (size_t)width * height * 3;
     HostRange* hr = host_range_ready(ppm_body_host, body);
     if (!hr) return fail("rt_gpu_deinterleave_ppm: the buffer is not a registered range of %zu bytes", body);
-    HIP_TRY(hipStreamWaitEvent(cs, hr->copied, 0));
-    if (uint8_t* dst = (uint8_t*)mapped(hr, ppm_body_host)) {
-        HIP_TRY(launch_deinterleave_u8(tiles, world, n_max, width, height, dst, cs));
-    } else {
-        DevBuf& f8 = g.ppm_stage;
-        if (ensure(f8, body)) return RT_FAILURE;
-        HIP_TRY(launch_deinterleave_u8(tiles, world, n_max, width, height, (uint8_t*)f8.p, cs));
-        HIP_TRY(hipMemcpyAsync(ppm_body_host, f8.p, body, hipMemcpyDeviceToHost, cs));
-    }
-    HIP_TRY(hipEventRecord(hr->copied, cs));
-    return RT_SUCCESS;
+    return body_to_host(tiles, world, n_max, width, height, hr, ppm_body_host, cs, g.ppm_stage);
 }
 
 int rt580_selftest_math(uint64_t seed, uint64_t n, uint64_t* mismatches) {
@@ -2050,6 +2068,17 @@ bool rccl_load() {
         if (r_ != ncclSuccess) return fail("%s: %s", #expr, g_rccl.GetErrorString(r_));         \
     } while (0)
 
+// The buffers of one split frame: per context its rows' AO-call counts, the
+// gathered counts of all, the rows' RNG bases and its row tile as int16 and as
+// PPM bytes; on context 0 the gathered tiles and the de-interleaved frame.
+struct SplitSet {
+    DevBuf rc[kMaxCtx], gat[kMaxCtx], base[kMaxCtx], t16[kMaxCtx], t8[kMaxCtx];  // on device k
+    DevBuf root, frame;                                                           // on device 0
+    hipEvent_t ready[kMaxCtx] = {};                                               // local transport
+    // context k's buffers (what split_count sizes and release_multi_ctx frees)
+    std::array<DevBuf*, 5> of(int k) { return {&rc[k], &gat[k], &base[k], &t16[k], &t8[k]}; }
+};
+
 // One split of the frame over n contexts (devices), with its RCCL communicator.
 struct Multi {
     int n = 0;
@@ -2057,20 +2086,21 @@ struct Multi {
     bool rccl = false;
     ncclComm_t comms[kMaxCtx] = {};
     uint64_t scene_of[kMaxCtx] = {};  // context 0's scene id last uploaded to context k
-    DevBuf row_calls[kMaxCtx], gathered[kMaxCtx], base[kMaxCtx], tile[kMaxCtx];  // on device k
-    DevBuf root_tiles, frame;                                                     // on device 0
-    hipEvent_t ready[kMaxCtx] = {};                                               // local transport
     // rt_gpu_render_multi_async: a ring of per-frame buffer sets. Frame f + kRing
     // reuses frame f's set only after every stream that read it has passed a
     // wait on frame f + 1's exchange (count gather: each context waits on every
     // other's event, or RCCL's own group), so any kRing >= 2 is safe; 3 matches
-    // the frames a context keeps in flight
+    // the frames a context keeps in flight. rt_gpu_render_multi takes the
+    // ring's next set like the async form: it drains every stream before it
+    // returns, so that is safe whenever an async frame is in flight
     static constexpr int kRing = 3;
     int ring = 0;
-    DevBuf a_rc[kRing][kMaxCtx], a_gat[kRing][kMaxCtx], a_base[kRing][kMaxCtx], a_t16[kRing][kMaxCtx],
-        a_t8[kRing][kMaxCtx];                                                    // on device k
-    DevBuf a_root8[kRing], a_frame8[kRing];                                      // on device 0
-    hipEvent_t a_ready[kRing][kMaxCtx] = {};                                     // local transport
+    SplitSet sets[kRing];
+    SplitSet& next_set() {
+        SplitSet& set = sets[ring];
+        ring = (ring + 1) % kRing;
+        return set;
+    }
 } g_multi;
 
 void destroy_comms() {
@@ -2090,15 +2120,10 @@ void release_multi_ctx(int k) {
     if (k < g_multi.n) destroy_comms();
     (void)hipSetDevice(g_ctx[k].device);
     (void)hipDeviceSynchronize();
-    for (DevBuf* b : {&g_multi.row_calls[k], &g_multi.gathered[k], &g_multi.base[k], &g_multi.tile[k]}) release(*b);
-    if (g_multi.ready[k]) (void)hipEventDestroy(g_multi.ready[k]);
-    g_multi.ready[k] = nullptr;
-    for (int r = 0; r < Multi::kRing; r++) {
-        for (DevBuf* b : {&g_multi.a_rc[r][k], &g_multi.a_gat[r][k], &g_multi.a_base[r][k], &g_multi.a_t16[r][k],
-                          &g_multi.a_t8[r][k]})
-            release(*b);
-        if (g_multi.a_ready[r][k]) (void)hipEventDestroy(g_multi.a_ready[r][k]);
-        g_multi.a_ready[r][k] = nullptr;
+    for (SplitSet& set : g_multi.sets) {
+        for (DevBuf* b : set.of(k)) release(*b);
+        if (set.ready[k]) (void)hipEventDestroy(set.ready[k]);
+        set.ready[k] = nullptr;
     }
     g_multi.scene_of[k] = 0;
 }
@@ -2108,11 +2133,9 @@ void release_multi() {
     for (int k = 0; k < kMaxCtx; k++) release_multi_ctx(k);
     if (g_ctx[0].inited) {
         (void)hipSetDevice(g_ctx[0].device);
-        release(g_multi.root_tiles);
-        release(g_multi.frame);
-        for (int r = 0; r < Multi::kRing; r++) {
-            release(g_multi.a_root8[r]);
-            release(g_multi.a_frame8[r]);
+        for (SplitSet& set : g_multi.sets) {
+            release(set.root);
+            release(set.frame);
         }
     }
 }
@@ -2128,87 +2151,108 @@ int transport_env() {
     return 0;
 }
 
-// The rest of the frame once every context has counted its rows (phase 2 +
-// gather + de-interleave + D2H); g_cur is restored by the caller.
-int multi_finish(const rt_render_params* p, int n, int n_max, int16_t* fb_out) {
-    const int H = p->height, W = p->width;
-    const size_t tile_bytes = (size_t)n_max * W * 6;
-    // exchange of the per-row AO-call counts (H int32 in all; the one step the
-    // serial RNG stream needs, Raytracer.h:592)
-    if (g_multi.rccl) {
-        RCCL_TRY(g_rccl.GroupStart());
-        for (int k = 0; k < n; k++) {
-            g_cur = k;
-            RCCL_TRY(g_rccl.AllGather(g_multi.row_calls[k].p, g_multi.gathered[k].p, (size_t)n_max, ncclInt32,
-                                      g_multi.comms[k], g.stream));
-        }
-        RCCL_TRY(g_rccl.GroupEnd());
-    } else {
-        for (int k = 0; k < n; k++) {
-            g_cur = k;
-            HIP_TRY(hipSetDevice(g.device));
-            HIP_TRY(hipEventRecord(g_multi.ready[k], g.stream));
-        }
-        for (int k = 0; k < n; k++) {
-            g_cur = k;
-            HIP_TRY(hipSetDevice(g.device));
-            for (int j = 0; j < n; j++) {
-                HIP_TRY(hipStreamWaitEvent(g.stream, g_multi.ready[j], 0));
-                HIP_TRY(hipMemcpyPeerAsync((char*)g_multi.gathered[k].p + (size_t)j * n_max * 4, g.device,
-                                           g_multi.row_calls[j].p, g_ctx[j].device, (size_t)n_max * 4, g.stream));
-            }
-        }
-    }
-    // phase 2 on every device: its rows' RNG bases, then shading
+// The phases of a split frame over contexts 0..n-1, each enqueued on every
+// context's stream with no wait; g_cur is restored by the entry point.
+
+// p with context k's interleaved rows selected
+rt_render_params split_params(const rt_render_params* p, int k, int n) {
+    rt_render_params pk = *p;
+    pk.row_begin = k;
+    pk.row_step = n;
+    pk.row_end = p->height;
+    return pk;
+}
+
+// phase 1 on every device: trace its interleaved rows, count their AO calls
+int split_count(SplitSet& set, const rt_render_params* p, int n, int n_max) {
+    const size_t W = (size_t)p->width;
+    const size_t bytes[] = {(size_t)n_max * 4, (size_t)n * n_max * 4, (size_t)n_max * 8, n_max * W * 6, n_max * W * 3};
     for (int k = 0; k < n; k++) {
         g_cur = k;
         HIP_TRY(hipSetDevice(g.device));
-        rt_render_params pk = *p;
-        pk.row_begin = k;
-        pk.row_step = n;
-        pk.row_end = H;
-        if (rt_gpu_row_bases((const int32_t*)g_multi.gathered[k].p, n, n_max, H, k, (uint64_t*)g_multi.base[k].p) ||
-            rt_gpu_shade_rows(&pk, (const uint64_t*)g_multi.base[k].p, (int16_t*)g_multi.tile[k].p))
+        if (!set.ready[k]) HIP_TRY(hipEventCreateWithFlags(&set.ready[k], hipEventDisableTiming));
+        const auto bufs = set.of(k);
+        static_assert(std::tuple_size<decltype(bufs)>::value == sizeof bytes / sizeof *bytes, "one size per buffer");
+        for (size_t i = 0; i < bufs.size(); i++)
+            if (ensure(*bufs[i], bytes[i])) return RT_FAILURE;
+        HIP_TRY(hipMemsetAsync(set.rc[k].p, 0, (size_t)n_max * 4, g.stream));  // padding rows count 0
+        const rt_render_params pk = split_params(p, k, n);
+        if (rt_gpu_count_rows(&pk, (uint32_t*)set.rc[k].p)) return RT_FAILURE;
+    }
+    return RT_SUCCESS;
+}
+
+// exchange of the per-row AO-call counts (H int32 in all; the one step the
+// serial RNG stream needs, Raytracer.h:592)
+int exchange_counts(SplitSet& set, int n, int n_max) {
+    if (g_multi.rccl) {
+        RCCL_TRY(g_rccl.GroupStart());
+        for (int k = 0; k < n; k++) {
+            g_cur = k;
+            RCCL_TRY(g_rccl.AllGather(set.rc[k].p, set.gat[k].p, (size_t)n_max, ncclInt32, g_multi.comms[k], g.stream));
+        }
+        RCCL_TRY(g_rccl.GroupEnd());
+        return RT_SUCCESS;
+    }
+    for (int k = 0; k < n; k++) {
+        g_cur = k;
+        HIP_TRY(hipSetDevice(g.device));
+        HIP_TRY(hipEventRecord(set.ready[k], g.stream));
+    }
+    for (int k = 0; k < n; k++) {
+        g_cur = k;
+        HIP_TRY(hipSetDevice(g.device));
+        for (int j = 0; j < n; j++) {
+            HIP_TRY(hipStreamWaitEvent(g.stream, set.ready[j], 0));
+            HIP_TRY(hipMemcpyPeerAsync((char*)set.gat[k].p + (size_t)j * n_max * 4, g.device, set.rc[j].p,
+                                       g_ctx[j].device, (size_t)n_max * 4, g.stream));
+        }
+    }
+    return RT_SUCCESS;
+}
+
+// phase 2 on every device: its rows' RNG bases, then shading into t16[k]
+int split_shade(SplitSet& set, const rt_render_params* p, int n, int n_max) {
+    for (int k = 0; k < n; k++) {
+        g_cur = k;
+        HIP_TRY(hipSetDevice(g.device));
+        const rt_render_params pk = split_params(p, k, n);
+        if (rt_gpu_row_bases((const int32_t*)set.gat[k].p, n, n_max, p->height, k, (uint64_t*)set.base[k].p) ||
+            rt_gpu_shade_rows(&pk, (const uint64_t*)set.base[k].p, (int16_t*)set.t16[k].p))
             return RT_FAILURE;
     }
-    // the int16 row tiles to device 0
+    return RT_SUCCESS;
+}
+
+// the row tiles (tiles[k] on device k, `bytes` each) to set.root on device 0,
+// on context 0's stream; leaves context 0 current
+int gather_tiles(SplitSet& set, const DevBuf* tiles, size_t bytes, int n) {
     g_cur = 0;
     HIP_TRY(hipSetDevice(g.device));
-    if (ensure(g_multi.root_tiles, tile_bytes * n) || ensure(g_multi.frame, (size_t)H * W * 6)) return RT_FAILURE;
-    HIP_TRY(hipMemcpyAsync(g_multi.root_tiles.p, g_multi.tile[0].p, tile_bytes, hipMemcpyDeviceToDevice, g.stream));
+    if (ensure(set.root, bytes * n)) return RT_FAILURE;
+    HIP_TRY(hipMemcpyAsync(set.root.p, tiles[0].p, bytes, hipMemcpyDeviceToDevice, g.stream));
     if (g_multi.rccl) {
         RCCL_TRY(g_rccl.GroupStart());
         for (int k = 1; k < n; k++) {
-            RCCL_TRY(g_rccl.Send(g_multi.tile[k].p, tile_bytes, ncclUint8, 0, g_multi.comms[k], g_ctx[k].stream));
-            RCCL_TRY(g_rccl.Recv((char*)g_multi.root_tiles.p + (size_t)k * tile_bytes, tile_bytes, ncclUint8, k,
-                                 g_multi.comms[0], g_ctx[0].stream));
+            RCCL_TRY(g_rccl.Send(tiles[k].p, bytes, ncclUint8, 0, g_multi.comms[k], g_ctx[k].stream));
+            RCCL_TRY(g_rccl.Recv((char*)set.root.p + (size_t)k * bytes, bytes, ncclUint8, k, g_multi.comms[0],
+                                 g_ctx[0].stream));
         }
         RCCL_TRY(g_rccl.GroupEnd());
-    } else {
-        for (int k = 1; k < n; k++) {
-            g_cur = k;
-            HIP_TRY(hipSetDevice(g.device));
-            HIP_TRY(hipEventRecord(g_multi.ready[k], g.stream));
-        }
-        g_cur = 0;
-        HIP_TRY(hipSetDevice(g.device));
-        for (int k = 1; k < n; k++) {
-            HIP_TRY(hipStreamWaitEvent(g.stream, g_multi.ready[k], 0));
-            HIP_TRY(hipMemcpyPeerAsync((char*)g_multi.root_tiles.p + (size_t)k * tile_bytes, g.device,
-                                       g_multi.tile[k].p, g_ctx[k].device, tile_bytes, g.stream));
-        }
+        return RT_SUCCESS;
     }
-    HIP_TRY(launch_deinterleave((const int16_t*)g_multi.root_tiles.p, n, n_max, W, H, (int16_t*)g_multi.frame.p,
-                                g.stream));
-    if (copy_out((const int16_t*)g_multi.frame.p, fb_out, (size_t)H * W * 6)) return RT_FAILURE;
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    for (int k = 1; k < n; k++) {  // the other devices' streams are idle again before the next frame
+    for (int k = 1; k < n; k++) {
         g_cur = k;
         HIP_TRY(hipSetDevice(g.device));
-        HIP_TRY(hipStreamSynchronize(g.stream));
+        HIP_TRY(hipEventRecord(set.ready[k], g.stream));
     }
     g_cur = 0;
     HIP_TRY(hipSetDevice(g.device));
+    for (int k = 1; k < n; k++) {
+        HIP_TRY(hipStreamWaitEvent(g.stream, set.ready[k], 0));
+        HIP_TRY(hipMemcpyPeerAsync((char*)set.root.p + (size_t)k * bytes, g.device, tiles[k].p, g_ctx[k].device, bytes,
+                                   g.stream));
+    }
     return RT_SUCCESS;
 }
 
@@ -2279,24 +2323,24 @@ int multi_render(const rt_render_params* p, int16_t* fb_out, int n, const int* d
     bool single = false;
     if (multi_setup(p, n, devices, single)) return RT_FAILURE;
     if (single) return rt_gpu_render(p, fb_out);
-    // phase 1 on every device: trace its interleaved rows, count their AO calls
     const int H = p->height, W = p->width;
     const int n_max = (H + n - 1) / n;
-    for (int k = 0; k < n; k++) {
+    SplitSet& set = g_multi.next_set();
+    if (split_count(set, p, n, n_max) || exchange_counts(set, n, n_max) || split_shade(set, p, n, n_max) ||
+        gather_tiles(set, set.t16, (size_t)n_max * W * 6, n) || ensure(set.frame, (size_t)H * W * 6))
+        return RT_FAILURE;
+    // the int16 row tiles de-interleaved, to the caller's memory
+    HIP_TRY(launch_deinterleave((const int16_t*)set.root.p, n, n_max, W, H, (int16_t*)set.frame.p, g.stream));
+    if (copy_out((const int16_t*)set.frame.p, fb_out, (size_t)H * W * 6)) return RT_FAILURE;
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    for (int k = 1; k < n; k++) {  // the other devices' streams are idle again before the next frame
         g_cur = k;
         HIP_TRY(hipSetDevice(g.device));
-        if (!g_multi.ready[k]) HIP_TRY(hipEventCreateWithFlags(&g_multi.ready[k], hipEventDisableTiming));
-        if (ensure(g_multi.row_calls[k], (size_t)n_max * 4) || ensure(g_multi.gathered[k], (size_t)n * n_max * 4) ||
-            ensure(g_multi.base[k], (size_t)n_max * 8) || ensure(g_multi.tile[k], (size_t)n_max * W * 6))
-            return RT_FAILURE;
-        HIP_TRY(hipMemsetAsync(g_multi.row_calls[k].p, 0, (size_t)n_max * 4, g.stream));  // padding rows count 0
-        rt_render_params pk = *p;
-        pk.row_begin = k;
-        pk.row_step = n;
-        pk.row_end = H;
-        if (rt_gpu_count_rows(&pk, (uint32_t*)g_multi.row_calls[k].p)) return RT_FAILURE;
+        HIP_TRY(hipStreamSynchronize(g.stream));
     }
-    return multi_finish(p, n, n_max, fb_out);
+    g_cur = 0;
+    HIP_TRY(hipSetDevice(g.device));
+    return RT_SUCCESS;
 }
 
 // One frame of rt_gpu_render_multi_async: the same phases as multi_render on
@@ -2312,103 +2356,21 @@ int multi_frame_async(const rt_render_params* p, uint8_t* ppm_host, int n, const
     if (single) return rt_gpu_render_async_ppm(p, ppm_host);
     const int H = p->height, W = p->width;
     const int n_max = (H + n - 1) / n;
-    const size_t t16 = (size_t)n_max * W * 6, t8 = (size_t)n_max * W * 3, body = (size_t)H * W * 3;
+    const size_t t8 = (size_t)n_max * W * 3, body = (size_t)H * W * 3;
     g_cur = 0;
     HostRange* hr = host_range_ready(ppm_host, body);
     if (!hr) return fail("rt_gpu_render_multi_async: the buffer is not a registered range of %zu bytes", body);
-    const int r = g_multi.ring;
-    g_multi.ring = (r + 1) % Multi::kRing;
-    // phase 1
-    for (int k = 0; k < n; k++) {
+    SplitSet& set = g_multi.next_set();
+    if (split_count(set, p, n, n_max) || exchange_counts(set, n, n_max) || split_shade(set, p, n, n_max))
+        return RT_FAILURE;
+    for (int k = 0; k < n; k++) {  // each tile as PPM bytes
         g_cur = k;
         HIP_TRY(hipSetDevice(g.device));
-        if (!g_multi.a_ready[r][k]) HIP_TRY(hipEventCreateWithFlags(&g_multi.a_ready[r][k], hipEventDisableTiming));
-        if (ensure(g_multi.a_rc[r][k], (size_t)n_max * 4) || ensure(g_multi.a_gat[r][k], (size_t)n * n_max * 4) ||
-            ensure(g_multi.a_base[r][k], (size_t)n_max * 8) || ensure(g_multi.a_t16[r][k], t16) ||
-            ensure(g_multi.a_t8[r][k], t8))
-            return RT_FAILURE;
-        HIP_TRY(hipMemsetAsync(g_multi.a_rc[r][k].p, 0, (size_t)n_max * 4, g.stream));
-        rt_render_params pk = *p;
-        pk.row_begin = k;
-        pk.row_step = n;
-        pk.row_end = H;
-        if (rt_gpu_count_rows(&pk, (uint32_t*)g_multi.a_rc[r][k].p)) return RT_FAILURE;
-    }
-    // the per-row AO-call counts, all-gathered
-    if (g_multi.rccl) {
-        RCCL_TRY(g_rccl.GroupStart());
-        for (int k = 0; k < n; k++) {
-            g_cur = k;
-            RCCL_TRY(g_rccl.AllGather(g_multi.a_rc[r][k].p, g_multi.a_gat[r][k].p, (size_t)n_max, ncclInt32,
-                                      g_multi.comms[k], g.stream));
-        }
-        RCCL_TRY(g_rccl.GroupEnd());
-    } else {
-        for (int k = 0; k < n; k++) {
-            g_cur = k;
-            HIP_TRY(hipSetDevice(g.device));
-            HIP_TRY(hipEventRecord(g_multi.a_ready[r][k], g.stream));
-        }
-        for (int k = 0; k < n; k++) {
-            g_cur = k;
-            HIP_TRY(hipSetDevice(g.device));
-            for (int j = 0; j < n; j++) {
-                HIP_TRY(hipStreamWaitEvent(g.stream, g_multi.a_ready[r][j], 0));
-                HIP_TRY(hipMemcpyPeerAsync((char*)g_multi.a_gat[r][k].p + (size_t)j * n_max * 4, g.device,
-                                           g_multi.a_rc[r][j].p, g_ctx[j].device, (size_t)n_max * 4, g.stream));
-            }
-        }
-    }
-    // phase 2, then each tile as PPM bytes
-    for (int k = 0; k < n; k++) {
-        g_cur = k;
-        HIP_TRY(hipSetDevice(g.device));
-        rt_render_params pk = *p;
-        pk.row_begin = k;
-        pk.row_step = n;
-        pk.row_end = H;
-        if (rt_gpu_row_bases((const int32_t*)g_multi.a_gat[r][k].p, n, n_max, H, k,
-                             (uint64_t*)g_multi.a_base[r][k].p) ||
-            rt_gpu_shade_rows(&pk, (const uint64_t*)g_multi.a_base[r][k].p, (int16_t*)g_multi.a_t16[r][k].p))
-            return RT_FAILURE;
-        HIP_TRY(launch_gamma_u8((const int16_t*)g_multi.a_t16[r][k].p, t8, (uint8_t*)g_multi.a_t8[r][k].p, g.stream));
+        HIP_TRY(launch_gamma_u8((const int16_t*)set.t16[k].p, t8, (uint8_t*)set.t8[k].p, g.stream));
     }
     // the tiles to device 0, de-interleaved, to the host
-    g_cur = 0;
-    HIP_TRY(hipSetDevice(g.device));
-    if (ensure(g_multi.a_root8[r], t8 * n) || ensure(g_multi.a_frame8[r], body)) return RT_FAILURE;
-    HIP_TRY(hipMemcpyAsync(g_multi.a_root8[r].p, g_multi.a_t8[r][0].p, t8, hipMemcpyDeviceToDevice, g.stream));
-    if (g_multi.rccl) {
-        RCCL_TRY(g_rccl.GroupStart());
-        for (int k = 1; k < n; k++) {
-            RCCL_TRY(g_rccl.Send(g_multi.a_t8[r][k].p, t8, ncclUint8, 0, g_multi.comms[k], g_ctx[k].stream));
-            RCCL_TRY(g_rccl.Recv((char*)g_multi.a_root8[r].p + (size_t)k * t8, t8, ncclUint8, k, g_multi.comms[0],
-                                 g_ctx[0].stream));
-        }
-        RCCL_TRY(g_rccl.GroupEnd());
-    } else {
-        for (int k = 1; k < n; k++) {
-            g_cur = k;
-            HIP_TRY(hipSetDevice(g.device));
-            HIP_TRY(hipEventRecord(g_multi.a_ready[r][k], g.stream));
-        }
-        g_cur = 0;
-        HIP_TRY(hipSetDevice(g.device));
-        for (int k = 1; k < n; k++) {
-            HIP_TRY(hipStreamWaitEvent(g.stream, g_multi.a_ready[r][k], 0));
-            HIP_TRY(hipMemcpyPeerAsync((char*)g_multi.a_root8[r].p + (size_t)k * t8, g.device, g_multi.a_t8[r][k].p,
-                                       g_ctx[k].device, t8, g.stream));
-        }
-    }
-    if (uint8_t* dst = (uint8_t*)mapped(hr, ppm_host)) {  // de-interleaved straight into the host range
-        HIP_TRY(hipStreamWaitEvent(g.stream, hr->copied, 0));
-        HIP_TRY(launch_deinterleave_u8((const uint8_t*)g_multi.a_root8[r].p, n, n_max, W, H, dst, g.stream));
-        HIP_TRY(hipEventRecord(hr->copied, g.stream));
-        return RT_SUCCESS;
-    }
-    HIP_TRY(launch_deinterleave_u8((const uint8_t*)g_multi.a_root8[r].p, n, n_max, W, H,
-                                   (uint8_t*)g_multi.a_frame8[r].p, g.stream));
-    return ordered_d2h(hr, ppm_host, g_multi.a_frame8[r].p, body, g.stream);
+    if (gather_tiles(set, set.t8, t8, n)) return RT_FAILURE;
+    return body_to_host((const uint8_t*)set.root.p, n, n_max, W, H, hr, ppm_host, g.stream, set.frame);
 }
 
 // ---------------------------------------------------------------- one process per GPU
@@ -2549,16 +2511,8 @@ int rank_gather_pending() {
         HostRange* hr = host_range_ready(g_rank.pend_host, body);
         if (!hr) return fail("rt_gpu_render_rank_async: the buffer is not a registered range of %zu bytes", body);
         HIP_TRY(hipStreamWaitEvent(hs, g_rank.recvd[r], 0));
-        HIP_TRY(hipStreamWaitEvent(hs, hr->copied, 0));
-        if (uint8_t* dst = (uint8_t*)mapped(hr, g_rank.pend_host)) {  // straight into the host range
-            HIP_TRY(launch_deinterleave_u8((const uint8_t*)g_rank.root8[r].p, n, n_max, W, H, dst, hs));
-        } else {
-            if (ensure(g.ppm_stage, body)) return RT_FAILURE;
-            HIP_TRY(launch_deinterleave_u8((const uint8_t*)g_rank.root8[r].p, n, n_max, W, H,
-                                           (uint8_t*)g.ppm_stage.p, hs));
-            HIP_TRY(hipMemcpyAsync(g_rank.pend_host, g.ppm_stage.p, body, hipMemcpyDeviceToHost, hs));
-        }
-        HIP_TRY(hipEventRecord(hr->copied, hs));
+        if (body_to_host((const uint8_t*)g_rank.root8[r].p, n, n_max, W, H, hr, g_rank.pend_host, hs, g.ppm_stage))
+            return RT_FAILURE;
         HIP_TRY(hipEventRecord(g_rank.written[r], hs));
         g_rank.written_valid[r] = true;
     } else if (g_rank.comm) {
@@ -2593,24 +2547,11 @@ int rank_frame(const rt_render_params* p, uint8_t* ppm_host) {
         ensure(g_rank.base[r], (size_t)n_max * 8) || ensure(g_rank.t8[r], t8) ||
         (rank == 0 && !sh && ensure(g_rank.root8[r], t8 * n)) || (sh && ensure(g_rank.bar[r], (size_t)n * 4)))
         return RT_FAILURE;
-    rt_render_params pk = *p;
-    pk.row_begin = rank;
-    pk.row_step = n;
-    pk.row_end = H;
+    const rt_render_params pk = split_params(p, rank, n);
     const int n_rows = n_selected_rows(&pk);
     // phase 1 on the frame's slot: this rank's rows traced, their AO calls
-    // counted (rt_gpu_count_rows' steps, the counts copied on the slot stream)
-    if (begin_slot(false, g.nslots)) return RT_FAILURE;
-    for (int attempt = 0; attempt < 4; attempt++) {
-        if (begin_frame()) return RT_FAILURE;
-        HIP_TRY(hipEventRecord(g.ev[EV_START], fs()));
-        if (trace_rows(&pk, pk.row_begin, pk.row_step, n_rows)) return RT_FAILURE;
-        bool retry = false;
-        if (check_capacity(&pk, retry)) return RT_FAILURE;
-        if (!retry) break;
-        if (attempt == 3) return fail("node capacity could not be sized");
-        if (g.profiling) g.prof_frames--;
-    }
+    // counted (rt_gpu_count_rows' pass, the counts copied on the slot stream)
+    if (count_pass(&pk, n_rows)) return RT_FAILURE;
     HIP_TRY(hipMemsetAsync(g_rank.rc[r].p, 0, (size_t)n_max * 4, fs()));  // padding rows count 0
     if (n_rows)
         HIP_TRY(hipMemcpyAsync(g_rank.rc[r].p, SL.row_calls.p, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, fs()));

@@ -170,14 +170,19 @@ def _registered_u8(n):
     return raw, raw[off:off + span][:n], span
 
 
-@pytest.mark.parametrize("G,transport", [(1, None), (2, None), (3, None), (1, "rccl")])
-def test_render_multi_async_frames_are_the_ppm_bodies(G, transport):
+@pytest.mark.parametrize("G,transport,off", [
+    pytest.param(1, None, 0, id="1-None"), pytest.param(2, None, 0, id="2-None"),
+    pytest.param(3, None, 0, id="3-None"), pytest.param(3, None, 8, id="3-None-off8"),
+    pytest.param(1, "rccl", 0, id="1-rccl")])
+def test_render_multi_async_frames_are_the_ppm_bodies(G, transport, off):
     """rt_gpu_render_multi_async (bench.py's step for every N): frames of two
     configurations queued over a ring of three registered u8 buffers with no
     wait in between -- after a synchronize each buffer holds the PPM body of the
     last frame queued into it, byte-equal to the single-GPU render mapped by the
     reference's gamma LUT; G = 1 is rt_gpu_render_async_ppm; an unregistered
-    buffer is refused."""
+    buffer is refused. off = 8: the body starts 8 bytes into its registered
+    range, an address the device mapping is not used for (not 16-byte aligned),
+    so the frame goes through the staging buffer and the ordered copy."""
     rt580 = helpers.rt580()
     lib = rt580.load()
     root = helpers.synthetic_root("cornell10k")
@@ -199,9 +204,10 @@ def test_render_multi_async_frames_are_the_ppm_bodies(G, transport):
     s = rts[0][0].scene()
     rt580.check(lib.rt_gpu_upload_scene(ctypes.byref(s)), "upload")
     devs = (ctypes.c_int * G)(*([0] * G))
-    bufs = [_registered_u8(w * h * 3) for _ in range(3)]
-    for _, buf, span in bufs:
-        rt580.check(lib.rt_gpu_host_register(buf.ctypes.data, span), "host_register")
+    regs = [_registered_u8(w * h * 3 + 16) for _ in range(3)]
+    for _, reg, span in regs:
+        rt580.check(lib.rt_gpu_host_register(reg.ctypes.data, span), "host_register")
+    bufs = [(raw, reg[off:off + w * h * 3], span) for raw, reg, span in regs]
     old = os.environ.get("RT580_MULTI_TRANSPORT")
     if transport:
         os.environ["RT580_MULTI_TRANSPORT"] = transport
@@ -225,19 +231,23 @@ def test_render_multi_async_frames_are_the_ppm_bodies(G, transport):
                 del os.environ["RT580_MULTI_TRANSPORT"]
             else:
                 os.environ["RT580_MULTI_TRANSPORT"] = old
-        for _, buf, _ in bufs:
-            lib.rt_gpu_host_unregister(buf.ctypes.data)
+        for _, reg, _ in regs:
+            lib.rt_gpu_host_unregister(reg.ctypes.data)
     for rt, _ in rts:
         rt.close()
 
 
-@pytest.mark.parametrize("world,w,h", [(1, 64, 48), (3, 53, 29), (8, 1920, 1080)])
-def test_deinterleave_ppm_into_registered_memory(world, w, h):
+@pytest.mark.parametrize("world,w,h,off", [
+    pytest.param(1, 64, 48, 0, id="1-64-48"), pytest.param(3, 53, 29, 0, id="3-53-29"),
+    pytest.param(3, 53, 29, 8, id="3-53-29-off8"), pytest.param(8, 1920, 1080, 0, id="8-1920-1080")])
+def test_deinterleave_ppm_into_registered_memory(world, w, h, off):
     """rt_gpu_deinterleave_ppm (rank 0's last step in rt580_dist.DistFrame): the
     u8 tiles of `world` interleaved row shares (tile r = rows r, r + world, ...,
     n_max rows, the last rows padding) land de-interleaved in a registered host
     range -- against numpy's de-interleave of the same random tiles; twice into
-    the same range in call order; an unregistered buffer is refused."""
+    the same range in call order; an unregistered buffer is refused. off = 8:
+    the body starts 8 bytes into the range, where the device mapping is not used
+    (not 16-byte aligned) and the body goes through the staging buffer."""
     import torch
     rt580 = helpers.rt580()
     lib = rt580.load()
@@ -248,8 +258,9 @@ def test_deinterleave_ppm_into_registered_memory(world, w, h):
     want = [t.transpose(0, 1).reshape(n_max * world, w, 3)[:h].numpy().reshape(-1) for t in tiles]
     dev = [t.cuda() for t in tiles]
     torch.cuda.synchronize()  # the tiles are on the device before the library's stream reads them
-    raw, buf, span = _registered_u8(w * h * 3)
-    rt580.check(lib.rt_gpu_host_register(buf.ctypes.data, span), "host_register")
+    raw, reg, span = _registered_u8(w * h * 3 + 16)
+    rt580.check(lib.rt_gpu_host_register(reg.ctypes.data, span), "host_register")
+    buf = reg[off:off + w * h * 3]
     try:
         for k in (0, 1):
             rt580.check(lib.rt_gpu_deinterleave_ppm(dev[k].data_ptr(), world, n_max, w, h, buf.ctypes.data, None),
@@ -260,4 +271,54 @@ def test_deinterleave_ppm_into_registered_memory(world, w, h):
         plain = np.zeros(w * h * 3, dtype=np.uint8)
         assert lib.rt_gpu_deinterleave_ppm(dev[0].data_ptr(), world, n_max, w, h, plain.ctypes.data, None) != 0
     finally:
-        lib.rt_gpu_host_unregister(buf.ctypes.data)
+        lib.rt_gpu_host_unregister(reg.ctypes.data)
+
+
+def test_render_multi_blocking_between_async_frames():
+    """rt_gpu_render_multi between rt_gpu_render_multi_async frames on one device
+    set (G = 3 on device 0; 29 rows: shares of 10/10/9, one padding row), with
+    no synchronize before it: both forms take their buffers from one ring. Two
+    async frames, the blocking frame, one more async frame with other params,
+    then a synchronize -- every buffer equals the single-GPU render of its
+    params (int16 for the blocking call, the gamma LUT's u8 for the others)."""
+    rt580 = helpers.rt580()
+    lib = rt580.load()
+    root = helpers.synthetic_root("cornell10k")
+    w, h, G = 53, 29, 3
+    cfg = [(4, 16), (2, 8)]
+    lut = rt580.gamma_lut()
+    full = [render_gpu("cornell10k.json", w, h, d, a, True, root=root)[0] for d, a in cfg]
+    want8 = [lut[f.astype(np.int64)].astype(np.uint8).reshape(-1) for f in full]
+    rts = []
+    for d, a in cfg:
+        rt = rt580.Raytracer(w, h, root)
+        assert rt.LoadSceneJSON("cornell10k.json") == 0
+        rt.set_depth(d)
+        rt.set_ao(a, True)
+        assert rt.InitializeRenderer() == 0
+        rts.append((rt, rt.render_params()))
+    s = rts[0][0].scene()
+    rt580.check(lib.rt_gpu_upload_scene(ctypes.byref(s)), "upload")
+    devs = (ctypes.c_int * G)(*([0] * G))
+    bufs = [_registered_u8(w * h * 3) for _ in range(3)]
+    for _, buf, span in bufs:
+        rt580.check(lib.rt_gpu_host_register(buf.ctypes.data, span), "host_register")
+    out16 = np.zeros(w * h * 3, dtype=np.int16)
+    try:
+        for _, buf, _ in bufs:
+            buf[:] = 7
+        for b, k in ((0, 0), (1, 0)):
+            rt580.check(lib.rt_gpu_render_multi_async(ctypes.byref(rts[k][1]), bufs[b][1].ctypes.data, G, devs),
+                        "rt_gpu_render_multi_async")
+        rt580.check(lib.rt_gpu_render_multi(ctypes.byref(rts[0][1]), out16.ctypes.data, G, devs), "rt_gpu_render_multi")
+        rt580.check(lib.rt_gpu_render_multi_async(ctypes.byref(rts[1][1]), bufs[2][1].ctypes.data, G, devs),
+                    "rt_gpu_render_multi_async")
+        rt580.check(lib.rt_gpu_synchronize(), "synchronize")
+        assert np.array_equal(out16.reshape(h, w, 3), full[0]), "the blocking frame"
+        for b, k in ((0, 0), (1, 0), (2, 1)):
+            assert np.array_equal(bufs[b][1], want8[k]), "buffer %d (config %d)" % (b, k)
+    finally:
+        for _, buf, _ in bufs:
+            lib.rt_gpu_host_unregister(buf.ctypes.data)
+    for rt, _ in rts:
+        rt.close()
