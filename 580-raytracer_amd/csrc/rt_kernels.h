@@ -25,7 +25,7 @@ struct DevScene {
     int use_bvh;   // triangle scenes: exact BVH queries (rt_isect.h) instead of brute force
     // The primitives in a fixed pseudo-random order: the any-hit scan of
     // far-origin rays reads them this way (any order gives the same boolean;
-    // accepted primitives come clustered by mesh in scene order, see far_scan_kernel).
+    // accepted primitives come clustered by mesh in scene order, see far_brute_any_split_kernel).
     const rt_prim* scan_prims;
     // scene indices of the shadow-casting (directional and point) lights, in
     // JSON order, for the host-side launch loop of the shadow passes; <= 8

@@ -16,8 +16,10 @@
 //   rank_kernel   per pixel: pre-order walk of the pixel's tree numbers its AO
 //        calls exactly as the reference's serial RNG consumes them (raster order,
 //        then pre-order, then lights) and records each call's RNG position.
-//   ao_kernel     flat over (AO call, sample): every lane one hemisphere sample,
+//   AO            flat over (AO call, sample): a hemisphere sample per item,
 //        any-hit against the scene; perfectly balanced (95% of all rays).
+//        Small scenes: ao_kernel_occ8; BVH scenes: ao_near_kernel (the rays),
+//        ao_trace_kernel / ao_late_kernel (near query), the sorted far pass.
 //   resolve_kernel per pixel: post-order int16 blend of the tree (the blend is
 //        non-linear, so it runs bottom-up after AO is known).
 // Scene loops stage primitives in LDS tiles read uniformly by the workgroup.
@@ -401,7 +403,7 @@ __device__ __forceinline__ void block_alloc2(uint32_t* counter, bool fa, bool fb
 // Rays whose origin is so far out (a child of one of the reference's far hits)
 // that a typical triangle cannot be culled (T <= 0) or the fat-ray margin
 // covers the scene: the reference's own loop over every primitive
-// (far_scan_kernel) is cheaper than any traversal for them. Routing only; the
+// (the far_brute_*_kernel scans, far_scan_kernel) is cheaper than any traversal for them. Routing only; the
 // results are the same.
 __device__ __forceinline__ bool far_origin(const DevScene& S, rv3 o) {
     const float oi = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
@@ -459,24 +461,146 @@ __device__ __forceinline__ FarTri load_far_tri(const FarTri* tris, int j) {
     return t;
 }
 
+// One entry of the far-hit queue (W.far_rays / far_keys / far_vals) at `slot`:
+// the ray, its tag (AO call, tree node or shadow-flag index), its t bound and
+// its sort key.
+__device__ __forceinline__ void far_queue_write(const DevScene& S, const DevWork& W, uint32_t slot, rv3 o, rv3 d,
+                                                uint32_t tag, float tmax, bool brute) {
+    W.far_rays[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, __uint_as_float(tag));
+    W.far_rays[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, tmax);
+    W.far_keys[slot] = brute ? RT_KEY_BRUTE : far_key(S.bv, o, d);
+    W.far_vals[slot] = slot;
+}
+
+// ---------------------------------------------------------------- speculative any-hit walk
+// bvh4_any_near_budget_state in speculative while-while form (Aila & Laine's
+// postponed leaves): the wave descends until every lane holds a leaf; a lane
+// that reaches one first keeps it and goes on descending from its stack in the
+// node iterations the wave spends on the others, so its next leaf is found in
+// steps that would otherwise idle; the leaf phase then tests the held leaf and,
+// when the lane's current entry is a leaf too, that one. The same nodes and
+// leaves as the ordinary walk, visited in another order and stopped at the
+// first hit: the same boolean. tools/simd_sim.cpp (100k field, budget 4): wave
+// node iterations 45.5 -> 32.8, leaf tests 7.8 -> 8.8. Needs the whole wave
+// (a vote ends the node phase): inactive lanes pass live = false.
+// 1 hit, 0 no hit, -1 undecided after `budget` leaf tests: the stack [0, sp) and
+// the entry (c, n) next (n > 0 a leaf) are the walk's state for ao_late_kernel.
+// (A second held leaf per lane, taken while the lane goes on descending with
+// one held: tools/simd_sim.cpp, 100k field, budget 4: wave node iterations
+// 32.6 -> 29.2, leaf tests 8.8 -> 9.1 -- a smaller step than the first held
+// leaf's, for two more live registers per lane. No kernel ever enabled it; not
+// kept.)
+template <class STK>
+__device__ __forceinline__ bool spec_pop(const STK& stk, int& sp, int32_t& c, int32_t& n) {
+    if (sp == 0) return false;
+    sp--;
+    const uint32_t e = stk.get_lds_first(sp);
+    c = (int32_t)(e & 0x7ffffffu);
+    n = (int32_t)(e >> 27);
+    return true;
+}
+
+// bvh4_any_spec_walk: the walk from the state (stack [0, sp), entry (c, n)),
+// as bvh4_any_near_resume_budget; bvh4_any_spec_budget_state: from the root,
+// after the brute list, as bvh4_any_near_budget_state.
+// BOUND: only hits with !(t > tmax) count (point-light shadow rays).
+template <bool BOUND = false, class STK>
+__device__ int bvh4_any_spec_walk(const BvhView& V, rv3 o, rv3 d, const STK& stk, int budget, bool live, int& sp,
+                                  int32_t& c, int32_t& n, float tmax = INFINITY) {
+    if (!live) return 0;
+    int r = 0;
+    const SlabRay sr = slab_ray(V, o, d);
+    int32_t pc = 0, pn = 0;  // the held leaf (pn > 0)
+    int visits = 0;
+    while (live) {
+        for (;;) {  // node phase
+            if (pn == 0 && n > 0) {
+                pc = c;
+                pn = n;
+                if (!spec_pop(stk, sp, c, n)) n = -1;
+            }
+            if (!__any(pn == 0 && n == 0)) break;  // every lane holds a leaf or has none left
+            if (n == 0) {  // one node iteration (speculative when the lane holds a leaf)
+                Node4 nd;
+                float t[4];
+                bool ok[4];
+                node4_slab(V.nodes4 + c, sr, t, ok, nd.link);
+#pragma unroll
+                for (int j = 0; j < 4; j++) ok[j] = (nd.link[j] != 0xffffffffu) & ok[j] & (!BOUND || !(t[j] > tmax));
+                int best = -1;
+                float bt = INFINITY;
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (ok[j] & ((best < 0) | (t[j] < bt))) {
+                        best = j;
+                        bt = t[j];
+                    }
+                bool take[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) take[j] = ok[j] & (j != best);
+                stk.push4(sp, nd.link, take);
+                if (best >= 0) {
+                    const uint32_t e = best == 0 ? nd.link[0] : best == 1 ? nd.link[1] : best == 2 ? nd.link[2] : nd.link[3];
+                    c = (int32_t)(e & 0x7ffffffu);
+                    n = (int32_t)(e >> 27);
+                } else if (!spec_pop(stk, sp, c, n)) {
+                    n = -1;
+                }
+            }
+        }
+        // leaf phase
+        bool h = false;
+        if (pn > 0) {
+            h = bvh4_leaf_hit(V, o, d, BOUND ? tmax : INFINITY, pc, pn);
+            visits++;
+            pn = 0;
+            if (!h && n > 0 && visits < budget) {  // the current entry is a leaf too
+                h = bvh4_leaf_hit(V, o, d, BOUND ? tmax : INFINITY, c, n);
+                visits++;
+                if (!spec_pop(stk, sp, c, n)) n = -1;
+            }
+        }
+        if (h) {
+            r = 1;
+            live = false;
+        } else if (n < 0) {
+            r = 0;
+            live = false;
+        } else if (visits >= budget) {
+            r = -1;
+            live = false;
+        }
+    }
+    return r;
+}
+
+template <bool BOUND = false, class STK>
+__device__ int bvh4_any_spec_budget_state(const BvhView& V, rv3 o, rv3 d, const STK& stk, int budget, bool live,
+                                          int& sp, int32_t& c, int32_t& n, float tmax = INFINITY) {
+    sp = 0;
+    c = 0;
+    n = 0;  // root (internal); n < 0: nothing left on this lane
+    if (live)
+        for (int k = 0; k < V.n_brute; k++)
+            if (prim_hit_within(V.all[V.brute[k]], o, d, BOUND ? tmax : INFINITY)) return 1;
+    if (live && (!V.has_tree || dir_zero(d))) live = false;
+    return bvh4_any_spec_walk<BOUND>(V, o, d, stk, budget, live, sp, c, n, tmax);
+}
+
 // ---------------------------------------------------------------- trace (one tree level)
 __device__ __forceinline__ int pixel_frame_row(const DevFrame& F, int lr) { return F.row_begin + lr * F.row_step; }
 
 // PHASE 0: the whole level in one pass (brute force, or BVH without sorted far
 // pass). BVH scenes with a plane tree split it: PHASE 1 = near closest hit,
 // provisional hit stored per node and rays that may still have a far hit
-// queued (sorted far_closest_kernel in between); PHASE 3 = the shadow ray of
+// queued (sorted far_cell_closest_kernel in between); PHASE 3 = the shadow ray of
 // directional light `light` (its index among the directional lights: `dl`):
 // near any-hit, the undecided rays queued for the sorted far pass, flags in
 // W.shadow; PHASE 2 = shading from the stored hit and shadow flags. Items
 // [i0, i1) of the level.
 // SCALAR (small brute-force scenes): wave-uniform scalar scene loads and the
 // division-free sign rejections (tri_test<SIGN>) instead of the LDS tile.
-
-template <int HOLD2, bool BOUND, class STK>
-__device__ int bvh4_any_spec_budget_state(const BvhView& V, rv3 o, rv3 d, const STK& stk, int budget, bool live,
-                                          int& sp, int32_t& c, int32_t& n, float tmax = INFINITY);
-
+//
 // PHASE 3 (shadow rays) walks the 4-wide tree in speculative while-while form
 // (bvh4_any_spec_budget_state, the whole wave; profiles/r05/ab/trace_spec.txt:
 // 283.5 -> 271.9 us per launch on the north-star frame, 451 -> 404 us on
@@ -557,10 +681,7 @@ __global__ void __launch_bounds__(TB) trace_kernel(DevScene S, DevFrame F, DevWo
                 qb = __shfl(qb, leader);
                 if (q) {
                     const uint32_t slot = qb + (uint32_t)__popcll(qm & lanemask_lt());
-                    W.far_rays[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, __uint_as_float(node));
-                    W.far_rays[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, 0.0f);
-                    W.far_keys[slot] = brute ? RT_KEY_BRUTE : far_key(S.bv, o, d);
-                    W.far_vals[slot] = slot;
+                    far_queue_write(S, W, slot, o, d, node, 0.0f, brute);
                 }
             }
             continue;
@@ -603,8 +724,8 @@ __global__ void __launch_bounds__(TB) trace_kernel(DevScene S, DevFrame F, DevWo
                 uint32_t sa[RT_BVH_STACK + 4 - NEAR_LDS];
                 int ssp = 0;
                 int32_t sc = 0, sn = 0;
-                nh = bvh4_any_spec_budget_state<0, true>(S.bv, so, L2, LdsStack<NEAR_LDS, TB>{&nstk[0][threadIdx.x], sa},
-                                                         1 << 30, lit && !brute, ssp, sc, sn, tmax) > 0;
+                nh = bvh4_any_spec_budget_state<true>(S.bv, so, L2, LdsStack<NEAR_LDS, TB>{&nstk[0][threadIdx.x], sa},
+                                                      1 << 30, lit && !brute, ssp, sc, sn, tmax) > 0;
             } else {
                 nh = lit && !brute && bvh_any_near(S.bv, so, L2, tmax);
             }
@@ -621,10 +742,7 @@ __global__ void __launch_bounds__(TB) trace_kernel(DevScene S, DevFrame F, DevWo
                 qb = __shfl(qb, leader);
                 if (q) {
                     const uint32_t slot = qb + (uint32_t)__popcll(qm & lanemask_lt());
-                    W.far_rays[2 * (size_t)slot] = make_float4(so.x, so.y, so.z, __uint_as_float(item - i0));
-                    W.far_rays[2 * (size_t)slot + 1] = make_float4(L2.x, L2.y, L2.z, tmax);
-                    W.far_keys[slot] = brute ? RT_KEY_BRUTE : far_key(S.bv, so, L2);
-                    W.far_vals[slot] = slot;
+                    far_queue_write(S, W, slot, so, L2, item - i0, tmax, brute);
                 }
             }
             continue;
@@ -905,35 +1023,30 @@ __device__ __forceinline__ void ao_draws(const DevFrame& F, const DevWork& W, ui
     }
 }
 
-// After an AO ray's any-hit query: BVH scenes queue the near misses for the
-// sorted far-hit pass (and count the far-origin rays); hits count towards the
-// call's occlusion (W.occ). With N a multiple of 64 a wave holds one call's
-// samples (items are aligned chunks), so one atomic per wave.
-template <bool BVH>
-__device__ __forceinline__ void ao_finish(const DevScene& S, const DevWork& W, uint32_t N, bool active, bool ao_brute,
-                                          bool hit, uint64_t c, rv3 o, rv3 d) {
-    if (BVH) {
-        // rays that miss every near triangle go to the sorted far-hit pass,
-        // unless their direction-grid cell is empty
-        const bool q = active && !hit && S.bv.has_far && (ao_brute || far_live(S.bv, o, d));
-        const uint64_t qm = __ballot(q);
-        const uint64_t bm = __ballot(ao_brute);
-        if (bm && (threadIdx.x & 63) == 0) atomicAdd(W.far_count + 1, (uint32_t)__popcll(bm));
-        if (qm) {
-            const int leader = __ffsll((unsigned long long)qm) - 1;
-            uint32_t base = 0;
-            if ((threadIdx.x & 63) == leader) base = atomicAdd(W.far_count, (uint32_t)__popcll(qm));
-            base = __shfl(base, leader);
-            if (q) {
-                const uint32_t slot = base + (uint32_t)__popcll(qm & lanemask_lt());
-                W.far_rays[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, __uint_as_float((uint32_t)c));
-                W.far_rays[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, INFINITY);  // .w: t bound
-                W.far_keys[slot] = ao_brute ? RT_KEY_BRUTE : far_key(S.bv, o, d);
-                W.far_vals[slot] = slot;
-            }
-        }
+// After a BVH scene's near any-hit query of AO ray (o, d) of call c: the rays
+// that miss every near triangle go to the sorted far-hit pass, unless their
+// direction-grid cell is empty; the far-origin rays among them are counted.
+// Whole wave.
+__device__ __forceinline__ void ao_far_push(const DevScene& S, const DevWork& W, bool active, bool ao_brute, bool hit,
+                                            uint64_t c, rv3 o, rv3 d) {
+    const bool q = active && !hit && S.bv.has_far && (ao_brute || far_live(S.bv, o, d));
+    const uint64_t qm = __ballot(q);
+    const uint64_t bm = __ballot(ao_brute);
+    if (bm && (threadIdx.x & 63) == 0) atomicAdd(W.far_count + 1, (uint32_t)__popcll(bm));
+    if (qm) {
+        const int leader = __ffsll((unsigned long long)qm) - 1;
+        uint32_t base = 0;
+        if ((threadIdx.x & 63) == leader) base = atomicAdd(W.far_count, (uint32_t)__popcll(qm));
+        base = __shfl(base, leader);
+        if (q) far_queue_write(S, W, base + (uint32_t)__popcll(qm & lanemask_lt()), o, d, (uint32_t)c, INFINITY, ao_brute);
     }
-    if ((N & 63u) == 0) {
+}
+
+// An AO ray's hit counts towards its call's occlusion (W.occ[c]). one_call:
+// the wave holds samples of one call only (N a multiple of 64 and items taken
+// in aligned chunks): one atomic for the wave, which must call it as a whole.
+__device__ __forceinline__ void ao_count(const DevWork& W, bool one_call, bool active, bool hit, uint64_t c) {
+    if (one_call) {
         const uint64_t m = __ballot(active && hit);
         if ((threadIdx.x & 63) == 0 && m) atomicAdd(&W.occ[c], (uint32_t)__popcll(m));
     } else if (active && hit) {
@@ -941,27 +1054,31 @@ __device__ __forceinline__ void ao_finish(const DevScene& S, const DevWork& W, u
     }
 }
 
+// The AO ray of hemisphere vector v at hit point hp
+// (CalculateAmbientOcclusion, Raytracer.cpp:323-326; the Ray constructor's
+// normalize, Raytracer.h:431-433).
+__device__ __forceinline__ void ao_ray(rv3 hp, rv3 v, rv3& o, rv3& d) {
+    o = v3_add(hp, v3_scale(v, 0.2f));
+    d = v3_normalize_unit(v);
+}
+
 // CalculateAmbientOcclusion (Raytracer.cpp:315-330) + RandomInHemisphere (:283-292)
-// + RandomUnitVector (:269-281): one lane per (call, sample).
-// VARIANT bits (A/B switches, results identical): 1 = sincos table in LDS,
-// 2 = scalar per-call data (readfirstlane), 4 = sign-decided triangle rejects,
-// 8 = scalar (wave-uniform) scene loop, 16 = 8-waves/SIMD register cap,
-// 512 = exact BVH queries (triangle scenes; rt_isect.h), 1024 = polynomial
-// sincos with exact glibc fallback (rt_ao_dir_xy), 2048 = range-restricted
-// sqrt/division sequences for the unit vectors (v3_normalize_unit), 4096 = with
-// 1024: samples whose fast rounding test fails are queued (W.aofix_*) for
-// ao_fix_kernel instead of running glibc's sincos inline (keeps the rarely
-// taken fallback's registers out of the hot loop).
-// AO items [item_begin, item_end) (item = call * N + sample).
-// One AO sample of ao_body: item -> its call c and the ray (o, d) of
-// CalculateAmbientOcclusion's hemisphere sample (RandomInHemisphere /
-// RandomUnitVector with the serial RNG's draws); ao_brute: a far-origin ray;
-// fix: the fast sincos's rounding test failed (VARIANT & 4096).
-template <int VARIANT>
-__device__ __forceinline__ void ao_sample(const DevScene& S, const DevFrame& F, const DevWork& W, const double* sct,
-                                          uint32_t N, bool pow2, int log2n, bool wave_per_call, uint64_t item,
-                                          bool active, uint64_t& c, rv3& o, rv3& d, bool& ao_brute, bool& fix,
-                                          rv3& vo, rv3& hpo, uint32_t& so) {
+// + RandomUnitVector (:269-281): one lane per (call, sample), item = call * N +
+// sample (pow2 / log2n: N a power of two is split without the division).
+// One AO sample: item -> its call c, its sample index s, the call's hit point
+// hp, the hemisphere vector v of CalculateAmbientOcclusion's sample
+// (RandomInHemisphere / RandomUnitVector with the serial RNG's draws) and its
+// ray (o, d); FAR (BVH scenes): ao_brute, a far-origin ray. The sequences are
+// the fast ones: rt_sqrt_nr and v3_normalize_unit (range-restricted sqrt /
+// division, rt_math.h) and the polynomial sincos (rt_fast_sincos), whose
+// rounding test decides `fix`: the sample is not exact and goes to
+// ao_fix_kernel (W.aofix_*) instead of running glibc's sincos inline, which
+// keeps the rarely taken fallback's registers out of the hot loop. An inactive
+// lane gets zeros.
+template <bool FAR>
+__device__ __forceinline__ void ao_sample(const DevScene& S, const DevFrame& F, const DevWork& W, uint32_t N, bool pow2,
+                                          int log2n, uint64_t item, bool active, uint64_t& c, uint32_t& so, rv3& vo,
+                                          rv3& hpo, rv3& o, rv3& d, bool& ao_brute, bool& fix) {
     c = 0;
     uint32_t s = 0;
     vo = v3(0, 0, 0);
@@ -973,162 +1090,172 @@ __device__ __forceinline__ void ao_sample(const DevScene& S, const DevFrame& F, 
     o = v3(0, 0, 0);
     d = v3(0, 0, 0);
     ao_brute = false;
-    fix = false;  // VARIANT & 4096: this sample goes to ao_fix_kernel
+    fix = false;
     if (active) {
-        // With N a multiple of 64 a wave serves one call: keep its data scalar.
         uint32_t cc = (uint32_t)c;
-        if (wave_per_call) cc = __builtin_amdgcn_readfirstlane(cc);
         uint32_t node = W.call_node[cc];
-        if (wave_per_call) node = __builtin_amdgcn_readfirstlane(node);
         const NodeRec& nd = W.nodes[node];
         rv3 hp = ld3(nd.hp), n = ld3(nd.n);
         uint64_t rbase = W.call_rng[cc];
-        if (wave_per_call) {
-            hp = v3(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, hp.x))),
-                    __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, hp.y))),
-                    __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, hp.z))));
-            n = v3(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, n.x))),
-                   __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, n.y))),
-                   __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, n.z))));
-            rbase = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(rbase >> 32)) << 32) |
-                    __builtin_amdgcn_readfirstlane((uint32_t)rbase);
-        }
         float u0, u1;
         ao_draws(F, W, rbase, s, u0, u1);
         // uniform_real_distribution<float>: canonical * (b - a) + a
         const float z = u0 * (1.0f - (-1.0f)) + (-1.0f);
         const float ang = u1 * (F.ao_angle_max - 0.0f) + 0.0f;
-        // Ranges for the 2048 sequences (rt_math.h): z is 0 or a multiple of
+        // Ranges for the fast sequences (rt_math.h): z is 0 or a multiple of
         // 2^-30 in [-1, 1), so 1 - z*z (float) is +0 or >= 2^-24 and r is 0 or
         // >= 2^-12; |cos|, |sin| of a float angle in [0, 2pi) are 0 or > 2^-27,
         // so v's components are 0 or in [2^-39, 1] and |v| ~ 1 (also after the
         // first normalize).
-        const float r = (VARIANT & 2048) ? rt_sqrt_nr(1 - z * z) : sqrtf(1 - z * z);
-        rv3 v;
-        if (VARIANT & 4096) {
-            double sa, ca;
-            rt_fast_sincos((double)ang, &sa, &ca);
-            const double X = (double)r * ca, Y = (double)r * sa;
-            const float fx = (float)X, fy = (float)Y;
-            fix = !(rt_f32_round_safe(X, fx) && rt_f32_round_safe(Y, fy));
-            v = v3(fx, fy, z);
-        } else if (VARIANT & 1024) {
-            float vx, vy;
-            rt_ao_dir_xy(rt_dev::rt_sincostab, r, ang, &vx, &vy);
-            v = v3(vx, vy, z);
-        } else {
-            double sa, ca;
-            rt_glibc_sincos_simd_t(sct, (double)ang, &sa, &ca);
-            v = v3((float)((double)r * ca), (float)((double)r * sa), z);
-        }
-        v = (VARIANT & 2048) ? v3_normalize_unit(v) : v3_normalize(v);
+        const float r = rt_sqrt_nr(1 - z * z);
+        double sa, ca;
+        rt_fast_sincos((double)ang, &sa, &ca);
+        const double X = (double)r * ca, Y = (double)r * sa;
+        const float fx = (float)X, fy = (float)Y;
+        fix = !(rt_f32_round_safe(X, fx) && rt_f32_round_safe(Y, fy));
+        rv3 v = v3_normalize_unit(v3(fx, fy, z));
         if (!(v3_dot(v, n) > 0.0f)) v = v3_neg(v);
-        o = v3_add(hp, v3_scale(v, 0.2f));
-        // Ray constructor (Raytracer.h:431-433)
-        d = (VARIANT & 2048) ? v3_normalize_unit(v) : v3_normalize(v);
-        if ((VARIANT & 512) && S.bv.has_far) ao_brute = far_origin(S, o);
+        ao_ray(hp, v, o, d);
+        if (FAR && S.bv.has_far) ao_brute = far_origin(S, o);
         vo = v;
         hpo = hp;
     }
     so = s;
 }
 
-template <int VARIANT>
-__device__ __forceinline__ void ao_body(const DevScene& S, const DevFrame& F, const DevWork& W,
-                                        uint64_t item_begin = 0, uint64_t item_end = ~0ull) {
-    __shared__ rt_prim tile[TILE];
-    __shared__ double sct_lds[440];  // glibc __sincostab, staged once per workgroup
-    const double* sct = rt_dev::rt_sincostab;
-    if (VARIANT & 1) {
-        for (int i = threadIdx.x; i < 440; i += TB) sct_lds[i] = rt_dev::rt_sincostab[i];
-        __syncthreads();
-        sct = sct_lds;
-    }
+// Items [b, e) of a BVH scene's AO: the generation pass of the split AO pass.
+// Per item the 16-byte ray record for ao_trace_kernel -- the sample's
+// hemisphere vector v and (call - the chunk's first call) | flag << 30 (0: no
+// ray, i.e. past the end or queued for ao_fix_kernel; 1: near query; 2: far
+// origin) -- and the call's hit point once per call (ao_record rebuilds o and
+// d). 8 waves per SIMD (100k 1080p AO time: uncapped 169 ms (103 VGPRs, 4
+// waves/SIMD), 5 waves: 161 ms, 6: 158 ms, 8: 149 ms; the spills of the capped
+// builds cost less than the latency they hide).
+__device__ __forceinline__ void ao_generate(const DevScene& S, const DevFrame& F, const DevWork& W,
+                                            uint64_t item_begin, uint64_t item_end) {
     const uint32_t N = (uint32_t)F.ao_samples;
     const uint64_t items_all = W.totals[0] * (uint64_t)N;
     const uint64_t items = item_end < items_all ? item_end : items_all;
     const bool pow2 = (N & (N - 1)) == 0;
     const int log2n = 31 - __clz((int)N);
-    const bool wave_per_call = (VARIANT & 2) && (N & 63u) == 0;
-    const bool resident = (VARIANT & (8 | 512)) ? true : stage_resident(S, tile);
-    // VARIANT & 32768: two samples per lane (items b0 + threadIdx.x and
-    // b0 + TB + threadIdx.x): the scene loop loads each primitive once for both
-    // rays, and the two rays' arithmetic is independent (more work in flight per
-    // wave, half the per-sample scalar loads and loop control)
-    constexpr int SPL = (VARIANT & 32768) ? 2 : 1;
+    constexpr int SPL = 1;
     for (uint64_t b0 = item_begin + (uint64_t)blockIdx.x * TB * SPL; b0 < items; b0 += (uint64_t)gridDim.x * TB * SPL) {
-        bool active[SPL], ao_brute[SPL], fix[SPL], hit[SPL];
+        bool active[SPL], ao_brute[SPL], fix[SPL];
         uint64_t c[SPL];
-        rv3 o[SPL], d[SPL], vv[SPL], hh[SPL];
-        uint32_t ss[SPL];
+        rv3 o[SPL], d[SPL], v[SPL], hp[SPL];
+        uint32_t s[SPL];
 #pragma unroll
         for (int k = 0; k < SPL; k++) {
             const uint64_t item = b0 + (uint64_t)k * TB + threadIdx.x;
             active[k] = item < items;
-            ao_sample<VARIANT>(S, F, W, sct, N, pow2, log2n, wave_per_call, item, active[k], c[k], o[k], d[k],
-                               ao_brute[k], fix[k], vv[k], hh[k], ss[k]);
+            ao_sample<true>(S, F, W, N, pow2, log2n, item, active[k], c[k], s[k], v[k], hp[k], o[k], d[k], ao_brute[k],
+                            fix[k]);
         }
 #pragma unroll
         for (int k = 0; k < SPL; k++) {
             const uint64_t item = b0 + (uint64_t)k * TB + threadIdx.x;
-            if (VARIANT & 4096) {
-                const uint64_t fm = __ballot(fix[k]);
-                if (fm) {
-                    const int leader = __ffsll((unsigned long long)fm) - 1;
-                    uint32_t fb = 0;
-                    if ((threadIdx.x & 63) == leader) fb = atomicAdd(W.aofix_count, (uint32_t)__popcll(fm));
-                    fb = __shfl(fb, leader);
-                    if (fix[k]) {
-                        const uint32_t slot = fb + (uint32_t)__popcll(fm & lanemask_lt());
-                        if (slot < W.aofix_cap) W.aofix_items[slot] = item;
-                        active[k] = false;
-                        ao_brute[k] = false;
-                    }
+            // the failing samples go to ao_fix_kernel: no ray here
+            const uint64_t fm = __ballot(fix[k]);
+            if (fm) {
+                const int leader = __ffsll((unsigned long long)fm) - 1;
+                uint32_t fb = 0;
+                if ((threadIdx.x & 63) == leader) fb = atomicAdd(W.aofix_count, (uint32_t)__popcll(fm));
+                fb = __shfl(fb, leader);
+                if (fix[k]) {
+                    const uint32_t slot = fb + (uint32_t)__popcll(fm & lanemask_lt());
+                    if (slot < W.aofix_cap) W.aofix_items[slot] = item;
+                    active[k] = false;
+                    ao_brute[k] = false;
                 }
             }
-            if (VARIANT & 16384) {
-                // generation only: the 16-byte ray record for ao_trace_kernel -- the
-                // sample's hemisphere vector v and (call - the chunk's first call) |
-                // flag << 30 (0: no ray, 1: near query, 2: far origin) -- and the
-                // call's hit point once per call (ao_record rebuilds o and d)
-                if (item < items) {
-                    const uint64_t c0 = item_begin / N;
-                    const uint32_t flag = active[k] ? (ao_brute[k] ? 2u : 1u) : 0u;
-                    W.ao_rays[item - item_begin] =
-                        make_float4(vv[k].x, vv[k].y, vv[k].z, __uint_as_float((uint32_t)(c[k] - c0) | (flag << 30)));
-                    if (ss[k] == 0u || item == item_begin)
-                        W.ao_hp[c[k] - c0] = make_float4(hh[k].x, hh[k].y, hh[k].z, 0.0f);
-                }
+            if (item < items) {
+                const uint64_t c0 = item_begin / N;
+                const uint32_t flag = active[k] ? (ao_brute[k] ? 2u : 1u) : 0u;
+                W.ao_rays[item - item_begin] =
+                    make_float4(v[k].x, v[k].y, v[k].z, __uint_as_float((uint32_t)(c[k] - c0) | (flag << 30)));
+                if (s[k] == 0u || item == item_begin)
+                    W.ao_hp[c[k] - c0] = make_float4(hp[k].x, hp[k].y, hp[k].z, 0.0f);
             }
         }
-        if (VARIANT & 16384) continue;
-        if (SPL == 2 && (VARIANT & 8) && !(VARIANT & 512)) {
-            any_hit_scalar2<(VARIANT & 4) != 0>(S, active[0], o[0], d[0], active[SPL - 1], o[SPL - 1], d[SPL - 1],
-                                                hit[0], hit[SPL - 1]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < SPL; k++)
-                hit[k] =
-#ifdef RT580_DIAG_NO_NEAR
-                    (VARIANT & 512) ? (active[k] && !ao_brute[k]) :  // DIAGNOSTIC build only: every AO ray occluded, no traversal
-#endif
-                    (VARIANT & 512) ? (active[k] && !ao_brute[k] && bvh_any_near(S.bv, o[k], d[k]))
-                  : (VARIANT & 8) ? any_hit_scalar<(VARIANT & 4) != 0>(S, active[k], o[k], d[k])
-                                  : any_hit<(VARIANT & 4) != 0>(S, tile, resident, active[k], o[k], d[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < SPL; k++)
-            ao_finish<(VARIANT & 512) != 0>(S, W, N, active[k], ao_brute[k], hit[k], c[k], o[k], d[k]);
     }
+}
+
+__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(8)))
+ao_near_kernel(DevScene S, DevFrame F, DevWork W, uint64_t b, uint64_t e) {
+    if (frame_poisoned(W)) return;
+    ao_generate(S, F, W, b, e);
+}
+
+// Small-scene AO (brute force), items of AO calls [*call_lo, *call_hi) (device,
+// may be null: from the first / to the last call; a row range of the frame --
+// its calls are contiguous): the wave-uniform scalar scene loop with the
+// sign-decided triangle rejections, samples that fail the rounding test left
+// to ao_fix_kernel.
+// Two samples per lane (items b0 + threadIdx.x and b0 + TB + threadIdx.x): the
+// scene loop loads each primitive once for both rays, and the two rays'
+// arithmetic is independent -- more work in flight per wave, half the
+// per-sample scalar loads and loop control (config 2: 1.519 / 1.539 vs 1.586 /
+// 1.582 ms per frame for one sample per lane, profiles/r05/ab/spl_*.json).
+// The register budget is capped for 8 waves per SIMD (SGPR <= 80 admits 8
+// workgroups per CU instead of 6).
+__device__ __forceinline__ void ao_small(const DevScene& S, const DevFrame& F, const DevWork& W, uint64_t item_begin,
+                                         uint64_t item_end) {
+    const uint32_t N = (uint32_t)F.ao_samples;
+    const uint64_t items_all = W.totals[0] * (uint64_t)N;
+    const uint64_t items = item_end < items_all ? item_end : items_all;
+    const bool pow2 = (N & (N - 1)) == 0;
+    const int log2n = 31 - __clz((int)N);
+    constexpr int SPL = 2;
+    for (uint64_t b0 = item_begin + (uint64_t)blockIdx.x * TB * SPL; b0 < items; b0 += (uint64_t)gridDim.x * TB * SPL) {
+        bool active[SPL], ao_brute[SPL], fix[SPL], hit[SPL];
+        uint64_t c[SPL];
+        rv3 o[SPL], d[SPL], v[SPL], hp[SPL];
+        uint32_t s[SPL];
+#pragma unroll
+        for (int k = 0; k < SPL; k++) {
+            const uint64_t item = b0 + (uint64_t)k * TB + threadIdx.x;
+            active[k] = item < items;
+            ao_sample<false>(S, F, W, N, pow2, log2n, item, active[k], c[k], s[k], v[k], hp[k], o[k], d[k], ao_brute[k],
+                             fix[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < SPL; k++) {
+            const uint64_t item = b0 + (uint64_t)k * TB + threadIdx.x;
+            // the failing samples go to ao_fix_kernel: not traced here
+            const uint64_t fm = __ballot(fix[k]);
+            if (fm) {
+                const int leader = __ffsll((unsigned long long)fm) - 1;
+                uint32_t fb = 0;
+                if ((threadIdx.x & 63) == leader) fb = atomicAdd(W.aofix_count, (uint32_t)__popcll(fm));
+                fb = __shfl(fb, leader);
+                if (fix[k]) {
+                    const uint32_t slot = fb + (uint32_t)__popcll(fm & lanemask_lt());
+                    if (slot < W.aofix_cap) W.aofix_items[slot] = item;
+                    active[k] = false;
+                    ao_brute[k] = false;
+                }
+            }
+        }
+        any_hit_scalar2<true>(S, active[0], o[0], d[0], active[1], o[1], d[1], hit[0], hit[1]);
+        // items are taken in aligned chunks: with N a multiple of 64 a wave holds one call's samples
+#pragma unroll
+        for (int k = 0; k < SPL; k++) ao_count(W, (N & 63u) == 0, active[k], hit[k], c[k]);
+    }
+}
+
+__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(8, 8)))
+ao_kernel_occ8(DevScene S, DevFrame F, DevWork W, const uint64_t* call_lo, const uint64_t* call_hi) {
+    const uint64_t N = (uint64_t)F.ao_samples;
+    ao_small(S, F, W, call_lo ? *call_lo * N : 0ull, call_hi ? *call_hi * N : ~0ull);
 }
 
 
 // ---------------------------------------------------------------- AO fix-up
-// Samples of ao_body<... | 4096> whose fast rounding test failed (rt_libm.h
+// Samples of ao_sample whose fast rounding test failed (rt_libm.h
 // rt_f32_round_safe; ~3e-5 of samples): the exact sample with glibc's sincos,
 // then the main pass's scene query. Brute-force scenes test every primitive;
 // BVH scenes run the near query and send misses (and far-origin rays) to the
-// chunk's sorted far queue, like ao_body's own misses.
+// chunk's sorted far queue, like ao_trace_kernel's own misses.
 __device__ void ao_fix_item(const DevScene& S, const DevFrame& F, const DevWork& W, uint64_t item) {
     const uint32_t N = (uint32_t)F.ao_samples;
     const uint64_t c = item / N;
@@ -1152,11 +1279,7 @@ __device__ void ao_fix_item(const DevScene& S, const DevFrame& F, const DevWork&
         hit = !brute && bvh_any_near(S.bv, o, d);
         if (!hit && S.bv.has_far && (brute || far_live(S.bv, o, d))) {
             if (brute) atomicAdd(W.far_count + 1, 1u);
-            const uint32_t slot = atomicAdd(W.far_count, 1u);
-            W.far_rays[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, __uint_as_float((uint32_t)c));
-            W.far_rays[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, INFINITY);
-            W.far_keys[slot] = brute ? RT_KEY_BRUTE : far_key(S.bv, o, d);
-            W.far_vals[slot] = slot;
+            far_queue_write(S, W, atomicAdd(W.far_count, 1u), o, d, (uint32_t)c, INFINITY, brute);
             return;
         }
     } else {
@@ -1197,155 +1320,11 @@ __global__ void __launch_bounds__(TB) ao_fix_kernel(DevScene S, DevFrame F, DevW
     }
 }
 
-// Occupancy-capped flavours of ao_near_kernel (RT580_NEAR_WPE=0|5|6|8 for A/B;
-// 100k 1080p AO time: uncapped 169 ms (103 VGPRs, 4 waves/SIMD), 5: 161 ms, 6: 158 ms,
-// 8: 149 ms; the spills of the capped builds cost less than the latency they hide).
-template <int WPE, int V = 512 | 1024 | 2048 | 4096>
-__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE)))
-ao_near_kernel_w(DevScene S, DevFrame F, DevWork W, uint64_t b, uint64_t e) {
-    if (frame_poisoned(W)) return;
-    ao_body<V>(S, F, W, b, e);
-}
-
-// bvh4_any_near_budget_state in speculative while-while form (Aila & Laine's
-// postponed leaves): the wave descends until every lane holds a leaf; a lane
-// that reaches one first keeps it and goes on descending from its stack in the
-// node iterations the wave spends on the others, so its next leaf is found in
-// steps that would otherwise idle; the leaf phase then tests the held leaf and,
-// when the lane's current entry is a leaf too, that one. The same nodes and
-// leaves as the ordinary walk, visited in another order and stopped at the
-// first hit: the same boolean. tools/simd_sim.cpp (100k field, budget 4): wave
-// node iterations 45.5 -> 32.8, leaf tests 7.8 -> 8.8. Needs the whole wave
-// (a vote ends the node phase): inactive lanes pass live = false.
-// 1 hit, 0 no hit, -1 undecided after `budget` leaf tests: the stack [0, sp) and
-// the entry (c, n) next (n > 0 a leaf) are the walk's state for ao_late_kernel.
-template <class STK>
-__device__ __forceinline__ bool spec_pop(const STK& stk, int& sp, int32_t& c, int32_t& n) {
-    if (sp == 0) return false;
-    sp--;
-    const uint32_t e = stk.get_lds_first(sp);
-    c = (int32_t)(e & 0x7ffffffu);
-    n = (int32_t)(e >> 27);
-    return true;
-}
-
-// bvh4_any_spec_walk: the walk from the state (stack [0, sp), entry (c, n)),
-// as bvh4_any_near_resume_budget; bvh4_any_spec_budget_state: from the root,
-// after the brute list, as bvh4_any_near_budget_state.
-// HOLD2: a lane holds up to two leaves (the second taken while it goes on
-// descending with one held); the leaf phase tests them in order, then the
-// current entry if it is a leaf. tools/simd_sim.cpp, 100k field, budget 4: wave
-// node iterations 32.6 -> 29.2, leaf tests 8.8 -> 9.1.
-template <int HOLD2 = 0, bool BOUND = false, class STK>
-__device__ int bvh4_any_spec_walk(const BvhView& V, rv3 o, rv3 d, const STK& stk, int budget, bool live, int& sp,
-                                  int32_t& c, int32_t& n, float tmax = INFINITY) {
-    if (!live) return 0;
-    int r = 0;
-    const SlabRay sr = slab_ray(V, o, d);
-    int32_t pc = 0, pn = 0;  // the held leaf (pn > 0)
-    int32_t qc = 0, qn = 0;  // the second held leaf (HOLD2)
-    int visits = 0;
-    while (live) {
-        for (;;) {  // node phase
-            if (pn == 0 && n > 0) {
-                pc = c;
-                pn = n;
-                if (!spec_pop(stk, sp, c, n)) n = -1;
-            }
-            if (HOLD2 && qn == 0 && pn > 0 && n > 0) {
-                qc = c;
-                qn = n;
-                if (!spec_pop(stk, sp, c, n)) n = -1;
-            }
-            if (!__any(pn == 0 && n == 0)) break;  // every lane holds a leaf or has none left
-            if (n == 0 && (!HOLD2 || qn == 0)) {  // one node iteration (speculative when the lane holds a leaf)
-                Node4 nd;
-                float t[4];
-                bool ok[4];
-                node4_slab(V.nodes4 + c, sr, t, ok, nd.link);
-#pragma unroll
-                for (int j = 0; j < 4; j++) ok[j] = (nd.link[j] != 0xffffffffu) & ok[j] & (!BOUND || !(t[j] > tmax));
-                int best = -1;
-                float bt = INFINITY;
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (ok[j] & ((best < 0) | (t[j] < bt))) {
-                        best = j;
-                        bt = t[j];
-                    }
-                bool take[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) take[j] = ok[j] & (j != best);
-                stk.push4(sp, nd.link, take);
-                if (best >= 0) {
-                    const uint32_t e = best == 0 ? nd.link[0] : best == 1 ? nd.link[1] : best == 2 ? nd.link[2] : nd.link[3];
-                    c = (int32_t)(e & 0x7ffffffu);
-                    n = (int32_t)(e >> 27);
-                } else if (!spec_pop(stk, sp, c, n)) {
-                    n = -1;
-                }
-            }
-        }
-        // leaf phase
-        bool h = false;
-        if (pn > 0) {
-            h = bvh4_leaf_hit(V, o, d, BOUND ? tmax : INFINITY, pc, pn);
-            visits++;
-            pn = 0;
-            if (HOLD2 && !h && qn > 0 && visits < budget) {
-                h = bvh4_leaf_hit(V, o, d, BOUND ? tmax : INFINITY, qc, qn);
-                visits++;
-                qn = 0;
-            }
-            if (!h && n > 0 && (!HOLD2 || qn == 0) && visits < budget) {  // the current entry is a leaf too
-                h = bvh4_leaf_hit(V, o, d, BOUND ? tmax : INFINITY, c, n);
-                visits++;
-                if (!spec_pop(stk, sp, c, n)) n = -1;
-            }
-        }
-        if (h) {
-            r = 1;
-            live = false;
-        } else if (n < 0 && (!HOLD2 || qn == 0)) {
-            r = 0;
-            live = false;
-        } else if (visits >= budget) {
-            if (HOLD2 && qn > 0) {  // the untested held leaf back into the walk's state
-                if (n < 0) {
-                    c = qc;
-                    n = qn;
-                } else {
-                    stk.put(sp, ((uint32_t)qn << 27) | (uint32_t)qc);
-                    sp++;
-                }
-                qn = 0;
-            }
-            r = -1;
-            live = false;
-        }
-    }
-    return r;
-}
-
-template <int HOLD2 = 0, bool BOUND = false, class STK>
-__device__ int bvh4_any_spec_budget_state(const BvhView& V, rv3 o, rv3 d, const STK& stk, int budget, bool live,
-                                          int& sp, int32_t& c, int32_t& n, float tmax) {
-    sp = 0;
-    c = 0;
-    n = 0;  // root (internal); n < 0: nothing left on this lane
-    if (live)
-        for (int k = 0; k < V.n_brute; k++)
-            if (prim_hit_within(V.all[V.brute[k]], o, d, BOUND ? tmax : INFINITY)) return 1;
-    if (live && (!V.has_tree || dir_zero(d))) live = false;
-    return bvh4_any_spec_walk<HOLD2, BOUND>(V, o, d, stk, budget, live, sp, c, n, tmax);
-}
-
-// The AO ray of a 16-byte record of the generation pass (ao_body, VARIANT &
-// 16384): origin hp + 0.2 v and direction normalize(v) by the generation's own
-// float operations (CalculateAmbientOcclusion, Raytracer.cpp:323-326; the Ray
-// constructor, Raytracer.h:431-433), so (o, d) are the bits the generation
-// computed; c = the call. Returns the flag (0: no ray, 1: near query, 2: far
-// origin). c0: the chunk's first call (its first item / N).
+// The AO ray of a 16-byte record of the generation pass (ao_near_kernel): the
+// generation's own float operations on its own v and hp (ao_ray), so (o, d)
+// are the bits the generation would have computed; c = the call. Returns the
+// flag (0: no ray, 1: near query, 2: far origin). c0: the chunk's first call
+// (its first item / N).
 __device__ __forceinline__ uint32_t ao_record(const DevWork& W, float4 r, uint64_t c0, rv3& o, rv3& d, uint64_t& c) {
     const uint32_t w = __float_as_uint(r.w), rel = w & 0x3fffffffu, flag = w >> 30;
     c = c0 + rel;
@@ -1353,31 +1332,37 @@ __device__ __forceinline__ uint32_t ao_record(const DevWork& W, float4 r, uint64
     d = v3(0, 0, 0);
     if (flag) {
         const float4 h = W.ao_hp[rel];
-        const rv3 v = v3(r.x, r.y, r.z);
-        o = v3_add(v3(h.x, h.y, h.z), v3_scale(v, 0.2f));
-        d = v3_normalize_unit(v);
+        ao_ray(v3(h.x, h.y, h.z), v3(r.x, r.y, r.z), o, d);
     }
     return flag;
 }
 
-// Split AO pass of BVH scenes: ao_near_kernel_w<.., V | 16384> writes each
-// item's ray (W.ao_rays); this kernel runs the near any-hit query over the
-// 4-wide tree with nothing else live, then ao_finish. Rays [0, n) of the chunk.
-// LDS_D: the first LDS_D traversal-stack entries of each lane live in LDS (a
-//   column per lane), the rest in scratch.
-// SORT: the workgroup takes SORT * TB consecutive samples (SORT * TB / N calls
-//   of neighbouring pixels) at a time and traces them in the order of an LDS
-//   counting sort by octahedral direction cell (2^KL x 2^KL): a wave then holds
-//   rays of similar direction from nearby origins, which share more of their
-//   paths (tools/simd_sim.cpp "block sort"). Hits are counted per lane.
-// BUDGET: a lane gives up after BUDGET leaf visits; its item and its walk so
-//   far (W.ao_state) go to W.ao_late, and ao_late_kernel resumes the walk, so
-//   a wave is not held by its few long traversals (tools/simd_sim.cpp "budget").
+// Split AO pass of BVH scenes: ao_near_kernel writes each item's ray
+// (W.ao_rays); this kernel runs the near any-hit query over the 4-wide tree
+// with nothing else live, then ao_far_push / ao_count. Rays [0, n) of the chunk.
 // The walk is in speculative while-while form (bvh4_any_spec_budget_state).
-template <int WPE, int LDS_D, int SORT, int KL, int BUDGET>
-__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE)))
+// 6 waves per SIMD for this kernel and ao_late_kernel (80 VGPRs with nothing
+// but the walk live; the late pass at 8 waves: north-star 37.58 ms, no faster).
+constexpr int kAoTraceWpe = 6;
+// The first kAoLdsStack traversal-stack entries of each lane live in LDS (a
+// column per lane), the rest in scratch (ao_trace_kernel and ao_late_kernel).
+constexpr int kAoLdsStack = 16;
+// The workgroup takes kAoSort * TB consecutive samples (kAoSort * TB / N calls
+// of neighbouring pixels) at a time and traces them in the order of an LDS
+// counting sort by octahedral direction cell (2^kAoSortCellLog2 squared): a
+// wave then holds rays of similar direction from nearby origins, which share
+// more of their paths (tools/simd_sim.cpp "block sort"). Hits are counted per
+// lane: a sorted wave's lanes are no longer one call's samples.
+constexpr int kAoSort = 8, kAoSortCellLog2 = 4;
+// A lane gives up after kAoBudget leaf visits; its item and its walk so far
+// (W.ao_state) go to W.ao_late, and ao_late_kernel resumes the walk, so a wave
+// is not held by its few long traversals (tools/simd_sim.cpp "budget"; AO per
+// frame at budget 3 / 4 / 6: Cornell 77.8 / 78.9 / 82.5 ms, 100k 55.8 / 54.5 /
+// 54.6 ms).
+constexpr int kAoBudget = 4;
+__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(kAoTraceWpe)))
 ao_trace_kernel(DevScene S, DevWork W, uint64_t n, uint64_t c0) {
-    static_assert(LDS_D > 0 && SORT > 0 && BUDGET > 0, "LDS stack, block sort, step budget");
+    constexpr int LDS_D = kAoLdsStack, SORT = kAoSort, KL = kAoSortCellLog2;
     if (frame_poisoned(W)) return;
     __shared__ uint32_t lstk[LDS_D][TB];
     constexpr int SN = SORT * TB;
@@ -1448,7 +1433,7 @@ ao_trace_kernel(DevScene S, DevWork W, uint64_t n, uint64_t c0) {
         const LdsStack<LDS_D, TB> stk{&lstk[0][threadIdx.x], stk_a};
         int sp = 0;
         int32_t wc = 0, wn = 0;
-        const int r = bvh4_any_spec_budget_state<0>(S.bv, o, d, stk, BUDGET, flag == 1u, sp, wc, wn);
+        const int r = bvh4_any_spec_budget_state(S.bv, o, d, stk, kAoBudget, flag == 1u, sp, wc, wn);
         const bool hit = r > 0, late = r < 0;
         const uint64_t lm = __ballot(late);
         if (lm) {
@@ -1468,8 +1453,8 @@ ao_trace_kernel(DevScene S, DevWork W, uint64_t n, uint64_t c0) {
                 }
             }
         }
-        // sorted: a wave's lanes are no longer one call's samples
-        ao_finish<true>(S, W, 1u, active && !late, ao_brute, hit, call, o, d);
+        ao_far_push(S, W, active && !late, ao_brute, hit, call, o, d);
+        ao_count(W, /*one_call=*/false, active && !late, hit, call);
     }
 }
 
@@ -1484,9 +1469,9 @@ ao_trace_kernel(DevScene S, DevWork W, uint64_t n, uint64_t c0) {
 // (8 waves per SIMD, since removed) queued ~2 % of its far-pass rays with
 // origins not their own when the origin stayed live across the walk; every
 // answer it computed was right ("The 8-wave late-pass defect").
-template <int WPE, int LDS_D>
-__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(WPE)))
+__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(kAoTraceWpe)))
 ao_late_kernel(DevScene S, DevWork W, uint64_t c0) {
+    constexpr int LDS_D = kAoLdsStack;
     if (frame_poisoned(W)) return;
     __shared__ uint32_t lstk[LDS_D][TB];
     const uint32_t cnt = W.ao_late_count[0];
@@ -1525,14 +1510,15 @@ ao_late_kernel(DevScene S, DevWork W, uint64_t c0) {
             for (int t = 0; t < S.bv.n_brute && !pre; t++) pre = prim_hit_within(S.bv.all[S.bv.brute[t]], o, d, INFINITY);
             go = !pre && S.bv.has_tree && !dir_zero(d);
         }
-        const bool hit = pre || bvh4_any_spec_walk<0>(S.bv, o, d, stk, 1 << 30, go, sp, wc, wn) > 0;
+        const bool hit = pre || bvh4_any_spec_walk(S.bv, o, d, stk, 1 << 30, go, sp, wc, wn) > 0;
         if (live) {
             const volatile float4* rv = W.ao_rays + i;
             r = make_float4(rv->x, rv->y, rv->z, rv->w);
         }
         rv3 o2, d2;
         (void)ao_record(W, r, c0, o2, d2, call);
-        ao_finish<true>(S, W, 1u, live, false, hit, call, o2, d2);
+        ao_far_push(S, W, live, false, hit, call, o2, d2);
+        ao_count(W, /*one_call=*/false, live, hit, call);
     }
 }
 
@@ -1742,11 +1728,9 @@ static const AuditBuf* audit_for(const DevWork& W) {
 // Each candidate gets far_candidate + the full reference test. Must be called
 // by the whole wave.
 #ifdef RT580_DIAGNOSTICS
-// DIAGNOSTIC build only: far_any_kernel statistics -- rays, grid rays, uniform
-// waves, per-lane waves, lanes' list entries, lock-step list steps (per wave:
-// the longest lane list / U), plane-tree rays, candidates passing
-// far_candidate, full tests that hit
-__device__ unsigned long long g_far_stats[9];
+// DIAGNOSTIC build only: far_cell_any_kernel's rays (in cells with a
+// candidate, and plane-tree rays) and those found hit
+__device__ unsigned long long g_far_stats[2];
 #ifdef RT580_DIAG_NO_STATS  // timing ablations: no per-pair atomics
 #define RT_FAR_STAT(k, v) ((void)0)
 #else
@@ -2085,7 +2069,7 @@ far_cell_any_kernel(DevScene S, DevWork W, uint32_t n, uint8_t* flag) {
             }
             RT_FAR_STAT(0, live ? 1 : 0);
             RT_CELL_STAT(1, lane == 0 && !cur.tree ? (uint64_t)nr * (uint64_t)n_cand : 0ull);
-            RT_FAR_STAT(8, hit ? 1 : 0);
+            RT_FAR_STAT(1, hit ? 1 : 0);
             if (hit) any_hit_out(W, flag, __float_as_uint(sray[wave][lane][0].w));
         }
         if (wn >= nwork) break;
@@ -2134,9 +2118,9 @@ __device__ __forceinline__ void cell_closest_tests(const DevScene& S, const floa
 // ray's (t, primitive) key with an LDS atomicMin (= lex_better's order). The
 // winner's barycentrics are then recomputed (tri_test's outputs do not depend
 // on its bound) and stored if it changed. Plane-tree items walk the tree
-// (far_tree_closest_wave). Against far_closest_kernel, whose per-lane list
-// walk makes a wave as slow as its longest cell list, one dependent
-// entry -> plane -> record chain per step.
+// (far_tree_closest_wave). (The ray-major form it replaced walked each lane's
+// own cell list: a wave as slow as its longest list, one dependent
+// entry -> plane -> record chain per step.)
 __global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(FAR_ANY_WPE)))
 far_cell_closest_kernel(DevScene S, DevWork W) {
     if (frame_poisoned(W)) return;
@@ -2488,7 +2472,7 @@ __global__ void __launch_bounds__(TB) far_brute_merge_kernel(DevScene S, DevWork
 // ray once another slice has found an acceptor for it (done[r], polled at the
 // start and every 8 steps); the first slice to find one claims the ray
 // (atomicOr on done[r]), so the AO call's occlusion count is raised once per
-// ray as in far_scan_kernel. The boolean does not depend on which record
+// ray. The boolean does not depend on which record
 // accepted. AO rays test their call's hint record first (slice 0).
 template <int R>
 __global__ void __launch_bounds__(TB) far_brute_any_split_kernel(DevScene S, DevWork W, uint32_t first, uint32_t nb,
@@ -2586,7 +2570,11 @@ constexpr uint32_t kBruteSlice = 4096;
 constexpr uint32_t kBruteWaves = 8192;
 constexpr int kBruteRays = 8;
 
-static int grid_for(uint64_t items, int cap);
+static int grid_for(uint64_t items, int cap) {
+    uint64_t b = (items + TB - 1) / TB;
+    if (b < 1) b = 1;
+    return (int)(b < (uint64_t)cap ? b : (uint64_t)cap);
+}
 
 // The brute any-hit scan of the far-origin rays [first, first + nb) of the
 // sorted queue (flag: shadow flags, or null: AO occlusion counts).
@@ -2611,17 +2599,6 @@ static hipError_t launch_brute_any(const DevScene& S, const DevWork& W, uint32_t
                            flag);
     }
     return hipGetLastError();
-}
-
-// Same kernel with the register budget capped for 8 waves per SIMD (SGPR <= 80
-// admits 8 workgroups per CU instead of 6).
-// call_lo / call_hi (device, may be null): only the items of AO calls
-// [*call_lo, *call_hi) (a row range of the frame: its calls are contiguous).
-template <int VARIANT>
-__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(8, 8)))
-ao_kernel_occ8(DevScene S, DevFrame F, DevWork W, const uint64_t* call_lo, const uint64_t* call_hi) {
-    const uint64_t N = (uint64_t)F.ao_samples;
-    ao_body<VARIANT>(S, F, W, call_lo ? *call_lo * N : 0ull, call_hi ? *call_hi * N : ~0ull);
 }
 
 // ---------------------------------------------------------------- resolve
@@ -2732,14 +2709,8 @@ hipError_t launch_row_bases(const int32_t* gathered, int world, int n_max, int h
     return hipGetLastError();
 }
 
-static int grid_for(uint64_t items, int cap) {
-    uint64_t b = (items + TB - 1) / TB;
-    if (b < 1) b = 1;
-    return (int)(b < (uint64_t)cap ? b : (uint64_t)cap);
-}
-
 // Workgroups of a recursion level > 0 (trace and resolve; grid-stride over the
-// level's count, which only the device knows): RT580_DEEP_GRID for A/B.
+// level's count, which only the device knows).
 constexpr int kDeepGrid = 512;  // 4096 / 1024 / 512: config 2 1.562 / 1.561 / 1.550 ms, its 8-way share 0.324 / 0.323 / 0.319
 
 // RT580_PROGRESS=1: a stderr line per trace level / AO chunk of the BVH path
@@ -3373,8 +3344,8 @@ hipError_t upload_minstd_table(hipStream_t s) {
 
 // ---------------------------------------------------------------- kernel timer
 // HIP events around each launch of the AO ray kernel (the scene query of every
-// AO sample: ao_kernel for small scenes, ao_near_kernel for BVH scenes), on the
-// stream it runs on, while rt_gpu_profile is on: bench.py's roofline divides
+// AO sample: ao_kernel_occ8 for small scenes, ao_trace_kernel + ao_late_kernel
+// for BVH scenes), on the stream it runs on, while rt_gpu_profile is on: bench.py's roofline divides
 // the kernel's work by these per-launch durations.
 namespace {
 struct KernelTimer {
@@ -3434,7 +3405,7 @@ void kernel_timer_release() {
 // Radix-sorted key bits: grid keys are cell << (24 - 2 L), so their low
 // 24 - 2 L bits are zero and the sort skips them (3 digit passes instead of
 // 4 at L = 10, 11); plane-tree keys then group by their top direction bits
-// only -- grouping, never a result (RT580_SORT_BITS=0: every bit, A/B).
+// only -- grouping, never a result.
 static int sort_begin_bit(const DevScene& S) {
     if (S.bv.grid_log2 <= 0) return 0;
     const int b = 24 - 2 * S.bv.grid_log2;
@@ -3619,10 +3590,23 @@ size_t far_sort_tmp_bytes(uint32_t cap) {
     return std::max(bytes, std::max(rle, scan));
 }
 
+// Exact recompute of the samples the fast pass queued (or, on queue overflow,
+// of every failing sample of items [b, e)); exits at once with nothing to do.
 hipError_t launch_ao_fix(const DevScene& S, const DevFrame& F, const DevWork& W, uint64_t b, uint64_t e,
-                         hipStream_t s, const uint64_t* call_lo = nullptr, const uint64_t* call_hi = nullptr);
+                         hipStream_t s, const uint64_t* call_lo = nullptr, const uint64_t* call_hi = nullptr) {
+    // a few hundred samples per frame at most (the queue; its overflow case
+    // re-tests every item of [b, e) grid-stride): a small grid exits at once
+    hipLaunchKernelGGL(ao_fix_kernel, dim3(64), dim3(TB), 0, s, S, F, W, b, e, call_lo, call_hi);
+    return hipGetLastError();
+}
+
+// Small-scene AO (ao_kernel_occ8) on 16384 workgroups (64 per CU; 8192 / 32768
+// within 1 %).
 hipError_t launch_ao_small(const DevScene& S, const DevFrame& F, const DevWork& W, hipStream_t s,
-                           const uint64_t* call_lo = nullptr, const uint64_t* call_hi = nullptr);
+                           const uint64_t* call_lo = nullptr, const uint64_t* call_hi = nullptr) {
+    hipLaunchKernelGGL(ao_kernel_occ8, dim3(16384), dim3(TB), 0, s, S, F, W, call_lo, call_hi);
+    return hipGetLastError();
+}
 
 hipError_t launch_ao(const DevScene& S, const DevFrame& F, const DevWork& W, hipStream_t s) {
     (void)hipGetLastError();  // launch checks below must not see a stale error
@@ -3662,8 +3646,7 @@ hipError_t launch_ao(const DevScene& S, const DevFrame& F, const DevWork& W, hip
             // the samples' rays (16-byte records + each call's hit point), then the budgeted near any-hit in
             // speculative form (ao_trace_kernel) and the late pass for the rays
             // out of budget (ao_late_kernel), timed together (kt_*)
-            constexpr int V = 512 | 1024 | 2048 | 4096 | 16384;
-            hipLaunchKernelGGL((ao_near_kernel_w<8, V>), dim3(grid_for(e1 - b, 8192)), dim3(TB), 0, s, S, F, W, b, e1);
+            hipLaunchKernelGGL(ao_near_kernel, dim3(grid_for(e1 - b, 8192)), dim3(TB), 0, s, S, F, W, b, e1);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipMemsetAsync(W.ao_late_count, 0, 8, s)) != hipSuccess) return e;
             kt_begin(s);
@@ -3672,12 +3655,11 @@ hipError_t launch_ao(const DevScene& S, const DevFrame& F, const DevWork& W, hip
             // (AO trace per 4 north-star frames, cap 4608 / 8192 / 16384 / 32768 /
             // 65536 / 131072: 92.4 / 90.8 / 89.7-89.8 / 88.1 / 88.0-88.2 / 88.0 ms;
             // Cornell 165.3 -> 164.6 ms at 65536)
-            hipLaunchKernelGGL((ao_trace_kernel<6, 16, 8, 4, 4>), dim3(grid_for(e1 - b, 65536)), dim3(TB), 0, s, S, W,
-                               e1 - b, c0);
+            hipLaunchKernelGGL(ao_trace_kernel, dim3(grid_for(e1 - b, 65536)), dim3(TB), 0, s, S, W, e1 - b, c0);
             // 12288 workgroups (~2 late rays per lane): late pass per 4 north-star
             // frames 1536 / 3072 / 4096 / 12288 / 24576 / 49152 workgroups:
             // 11.93 / 11.49 / 11.15-11.24 / 10.47-10.55 / 11.04 / 10.82 ms
-            hipLaunchKernelGGL((ao_late_kernel<6, 16>), dim3(12288), dim3(TB), 0, s, S, W, c0);
+            hipLaunchKernelGGL(ao_late_kernel, dim3(12288), dim3(TB), 0, s, S, W, c0);
             kt_end(s, e1 - b);
             if ((e = hipGetLastError()) != hipSuccess) return e;
 #ifdef RT580_DIAGNOSTICS
@@ -3716,13 +3698,11 @@ hipError_t launch_ao(const DevScene& S, const DevFrame& F, const DevWork& W, hip
             if ((e = launch_far_cells(S, W, nq, (uint8_t*)nullptr, s)) != hipSuccess) return e;
 #ifdef RT580_DIAGNOSTICS
             {
-                unsigned long long st[9];
+                unsigned long long st[2];
                 if (hipMemcpyFromSymbolAsync(st, HIP_SYMBOL(g_far_stats), sizeof st, 0, hipMemcpyDeviceToHost, s) ==
                         hipSuccess &&
                     hipStreamSynchronize(s) == hipSuccess)
-                    progress("far_any so far: rays %llu grid %llu uniform waves %llu lane waves %llu list entries %llu "
-                             "lock-step steps %llu tree rays %llu candidates %llu hits %llu",
-                             st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8]);
+                    progress("far cell pass so far: rays %llu hits %llu", st[0], st[1]);
                 unsigned long long cs[3];
                 if (hipMemcpyFromSymbolAsync(cs, HIP_SYMBOL(g_cell_stats), sizeof cs, 0, hipMemcpyDeviceToHost, s) ==
                         hipSuccess &&
@@ -3757,29 +3737,6 @@ hipError_t launch_ao_calls(const DevScene& S, const DevFrame& F, const DevWork& 
     return launch_ao_fix(S, F, W, 0, ~0ull, s, call_lo, call_hi);
 }
 
-// Exact recompute of the samples the fast pass queued (or, on queue overflow,
-// of every failing sample of items [b, e)); exits at once with nothing to do.
-hipError_t launch_ao_fix(const DevScene& S, const DevFrame& F, const DevWork& W, uint64_t b, uint64_t e,
-                         hipStream_t s, const uint64_t* call_lo, const uint64_t* call_hi) {
-    // a few hundred samples per frame at most (the queue; its overflow case
-    // re-tests every item of [b, e) grid-stride): a small grid exits at once
-    hipLaunchKernelGGL(ao_fix_kernel, dim3(64), dim3(TB), 0, s, S, F, W, b, e, call_lo, call_hi);
-    return hipGetLastError();
-}
-
-// Small-scene AO (brute force): the wave-uniform scalar scene loop, sign-decided
-// rejections, the fast sincos / unit-vector sequences with the exact fix-up
-// queue, two samples per lane, 8 waves per SIMD (ao_kernel_occ8; config 2:
-// 1.519 / 1.539 vs 1.586 / 1.582 ms per frame for one sample per lane,
-// profiles/r05/ab/spl_*.json). 16384 workgroups (64 per CU; 8192 / 32768
-// within 1 %).
-hipError_t launch_ao_small(const DevScene& S, const DevFrame& F, const DevWork& W, hipStream_t s,
-                           const uint64_t* call_lo, const uint64_t* call_hi) {
-    constexpr int V = 4 | 8 | 1024 | 2048 | 4096 | 32768;
-    hipLaunchKernelGGL(ao_kernel_occ8<V>, dim3(16384), dim3(TB), 0, s, S, F, W, call_lo, call_hi);
-    return hipGetLastError();
-}
-
 hipError_t launch_resolve(const DevScene& S, const DevFrame& F, const DevWork& W, int16_t* fb, hipStream_t s) {
     const uint64_t npix = (uint64_t)F.n_rows * F.width;
     if (npix == 0) return hipSuccess;
@@ -3808,7 +3765,7 @@ hipError_t launch_copy_rows(const int16_t* src, int width, int row_begin, int ro
 }  // namespace rt580
 
 #ifdef RT580_DIAGNOSTICS
-// DIAGNOSTIC build only: the RT580_AO_VERIFY totals (ao_verify_kernel's out[0..63])
+// DIAGNOSTIC build only: the RT580_AO_VERIFY totals (the ao_audit_*_kernel's out[0..63])
 // since the last call, after a device-wide sync; then zeroed. 1: verification off.
 extern "C" int rt580_diag_ao_verify(unsigned long long* out64) {
     if (!rt580::g_verify_out) return 1;

@@ -89,7 +89,7 @@ __device__ __forceinline__ bool rt_div_nr_ok(float n) {
     const float a = fabsf(n);
     return n == 0.0f || (a >= 0x1p-60f && a <= 4.0f);
 }
-// Callers guarantee the range: the AO sampler's vectors (rt_kernels.hip ao_body).
+// Callers guarantee the range: the AO sampler's vectors (rt_kernels.hip ao_sample).
 __device__ __forceinline__ rv3 v3_normalize_unit(rv3 a) {
     const float s = a.x * a.x + a.y * a.y + a.z * a.z;
     const float len = rt_sqrt_nr(s);

@@ -1214,7 +1214,7 @@ int rt_gpu_upload_scene(const rt_scene_soa* s) {
              upload_vec(g.grid2_items, g.bvh.grid2_items, "the half-resolution grid lists")))
             return RT_FAILURE;
         if (g.bvh_ok && !g.bvh.far_nodes.empty()) {
-            // The any-hit scan order of far-origin rays (far_scan_kernel): a fixed
+            // The any-hit scan order of far-origin rays (far_brute_any_split_kernel): a fixed
             // shuffle of the scene. Such a ray (origin ~1e6 out, from one of the
             // reference's far hits) is accepted by hundreds to thousands of
             // primitives, but often only by one mesh's: in scene order the first

@@ -322,7 +322,8 @@ int rt_gpu_last_stats(rt_render_stats* stats);
 int rt_gpu_profile(int enable);
 int rt_gpu_profile_read(double* ms_trace, double* ms_rank, double* ms_ao, double* ms_resolve, int* frames);
 /* While profiling: HIP events around every launch of the AO ray kernel (the
- * scene query of each AO sample: ao_kernel, or ao_near_kernel for BVH scenes),
+ * scene query of each AO sample: ao_kernel_occ8, or ao_trace_kernel and
+ * ao_late_kernel for BVH scenes),
  * on the stream it runs on. Sum of their durations, number of launches and the
  * AO rays they covered, since rt_gpu_profile(1) (ao_rays counts the chunked BVH
  * launches only; a small-scene frame is one launch over all of its AO rays,

@@ -40,7 +40,7 @@ def main():
     name = max((k for k in ks if k.startswith(("ao_kernel", "ao_near_kernel", "ao_trace_kernel"))), key=lambda k: ks[k]["total_ns"])
     k = dict(ks[name])
     c = dict(k["counters"])
-    # a step-budgeted AO trace pass (ao_trace_kernel<..., BUDGET>) is followed by
+    # a step-budgeted AO trace pass (ao_trace_kernel, kAoBudget) is followed by
     # ao_late_kernel for the rays it left (one launch each per chunk; the live
     # HIP-event timer spans both): the AO ray kernel is the pair
     late = [n for n in ks if n.startswith("ao_late_kernel")]

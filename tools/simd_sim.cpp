@@ -1,7 +1,7 @@
 // SIMD-efficiency model of the AO any-hit traversal (development tool).
 //
 // Casts AO-style rays in waves of 64 as the GPU forms them (one hit point per
-// wave, 64 cosine-free hemisphere directions, like ao_body's items of one
+// wave, 64 cosine-free hemisphere directions, like the AO items of one
 // call) through the 4-wide traversal of rt_isect.h, records each lane's steps
 // (a step = inner-node iterations down to a leaf, then the leaf's triangle
 // tests), and prices a wave as lock-step execution of the while-while loop:
